@@ -5,9 +5,10 @@ torch.distributed.run, one rank per GPU over RCCL; WORLD_SIZE must equal --gpus)
 environment, by this script itself (spawn_ranks).  A bench "step" is ONE ROUND of the reference's round-robin alternation
 (cls batch, det batch, seg batch — SURVEY.md §8d), i.e. 3 train iterations = 3*B images per GPU,
 each with forward, loss, backward, gradient exchange, global-norm clip and AdamW.  Prints one JSON
-line on rank 0 (contract in the task statement): images/sec whole-job, the roofline of the MSDA
-forward kernel measured with HIP events inside the timed region, and the CPU baseline (the
-oracle on the host cores, one round of the same workload).
+line on rank 0: images/sec whole-job and the milliseconds of one timed step.  A plain run does nothing else: set-up,
+W warm-up steps, K timed steps, the line.  With --full it also reports the per-task device times of the timed steps, the
+per-kernel rooflines (eager profiled rounds run after the timed region) and the CPU baseline (the oracle on the host
+cores, one round of the same workload).  --dump-outputs DIR writes what the last timed step computed as .npy files.
 """
 import argparse
 import contextlib
@@ -46,8 +47,13 @@ def parse():
                          'bs=4); swinb1024 = configs[4] (Swin-B backbone, cls+det+seg round at 1024x1024 bs=1)')
     ap.add_argument('--size', type=int, default=None, help='override the workload\'s image size')
     ap.add_argument('--batch', type=int, default=None, help='override the workload\'s per-task batch size')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true', help='skip the eager profiled rounds after the timed region')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: per-task times, the per-kernel rooflines (eager '
+                         'profiled rounds after the timed region) and the CPU baseline (a child process); off by default')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(with --full) skip the CPU baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='(with --full) skip the eager profiled rounds after the timed region')
     ap.add_argument('--roofline-rounds', type=int, default=2)
     ap.add_argument('--roofline-hold-ms', type=float, default=60.0,
                     help='stream hold ahead of each eager roofline iteration so that its launches queue up')
@@ -66,6 +72,8 @@ def parse():
                          'the compute stream after backward; overlap = bucket all-reduces on RCCL\'s stream under backward '
                          '(torch DDP\'s form). Default: RSCOTR_DIST_INLINE, else inline')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
     w = WORKLOADS[a.workload]
     a.size = a.size or w['size']
     a.batch = a.batch or w['batch']
@@ -160,6 +168,38 @@ def cpu_baseline(size, batch, rounds, workload='mtl512', limit_s=420):
                     sample=f'one round did not finish within {limit_s}s on the host cores')
 
 
+DUMP_SAMPLE = 1 << 22  # elements of the parameter / gradient samples written by --dump-outputs (16 MB each in fp32)
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir, model, last):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float .npy files under out_dir.
+    * log_vars.<task>.<dataset>.<name>.npy (float64, 0-d): every logged loss / statistic of each iteration of that step;
+    * params_sample.npy (float32): the parameters the step left, a fixed seeded sample of DUMP_SAMPLE elements of all
+      parameters concatenated in model.named_parameters() order (the same positions in every run of the same workload);
+    * grads_sample.npy (float32): the gradients of the step's last iteration at the same positions.
+    Under 64 MB in all."""
+    import re
+    os.makedirs(out_dir, exist_ok=True)
+    for task, out in last.items():
+        for k, v in dict(out['log_vars']).items():
+            name = re.sub(r'[^A-Za-z0-9._-]', '_', k)
+            np.save(os.path.join(out_dir, f'log_vars.{name}.npy'), np.asarray(float(v), dtype=np.float64))
+    params = [p for _, p in model.named_parameters()]
+    total = sum(p.numel() for p in params)
+    if total <= DUMP_SAMPLE:
+        idx = torch.arange(total)
+    else:
+        idx = torch.randint(total, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+    idx = idx.to(params[0].device)
+    with torch.no_grad():
+        flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+        np.save(os.path.join(out_dir, 'params_sample.npy'), flat_p[idx].cpu().numpy())
+        del flat_p
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+        np.save(os.path.join(out_dir, 'grads_sample.npy'), flat_g[idx].cpu().numpy())
+
+
 def spawn_ranks(a):
     """`python bench.py --gpus N` started by hand (no launcher in the environment): start the N ranks — what the reference's
     `init_dist(args.launcher, ...)` expects a launcher to have done (tools/train.py:173-182) — by re-running this command under
@@ -239,8 +279,9 @@ def main():
     runner = build_runner(model, cfg, loader, logger=lambda m: print(m, file=sys.stderr, flush=True))  # (stdout carries ONE JSON line)
 
     hold = dict(cycles=0)  # > 0: park the stream this many spin cycles before every iteration (roofline rounds)
-    marks = []  # timed region only: (task, HIP event recorded after the iteration) -> per-task step times
+    marks = []  # timed region only, --full: (task, HIP event recorded after the iteration) -> per-task step times
     timing = dict(on=False)
+    last = {}  # task -> what train_iter() returned for it, most recent round (--dump-outputs)
 
     def one_round():
         for _ in range(ntask):
@@ -254,7 +295,8 @@ def main():
             if a.verbose:
                 torch.cuda.synchronize()
             t_it = time.perf_counter()
-            runner.train_iter()
+            out = runner.train_iter()
+            last[runner.last_task] = out
             if timing['on']:  # an event record costs the host ~1 us and the stream nothing
                 ev = torch.cuda.Event(enable_timing=True)
                 ev.record()
@@ -280,12 +322,13 @@ def main():
         dist.barrier()
     from rscotr_amd._lib import lib
     eager_timed = not runner.graphed  # no graphs (RSCOTR_GRAPHS=0): the launch-site events ride in the timed region
-    if eager_timed and rank == 0 and not a.no_roofline:
+    roofline = a.full and not a.no_roofline
+    if eager_timed and rank == 0 and roofline:
         lib.call('rscotr_prof_enable', PROF_EVERY_GEMM, 1, 1, 8192)
     torch.cuda.synchronize()
     ev0 = torch.cuda.Event(enable_timing=True)
     ev0.record()
-    timing['on'] = True
+    timing['on'] = a.full
     t0 = time.perf_counter()
     for _ in range(a.steps):
         one_round()
@@ -299,7 +342,9 @@ def main():
         per_task.setdefault(task, []).append(prev.elapsed_time(ev))
         prev = ev
     per_task = {t: round(sum(v) / len(v), 3) for t, v in per_task.items()}
-    if runner.graphed and not a.no_roofline:  # every rank runs these rounds (they hold collectives); rank 0 records
+    if a.dump_outputs and rank == 0:  # before the roofline rounds below, which go on training the model
+        dump_outputs(a.dump_outputs, model, last)
+    if runner.graphed and roofline:  # every rank runs these rounds (they hold collectives); rank 0 records
         # The timed region replays hipGraphs, which cannot carry per-kernel HIP events.  The rooflines are
         # therefore sampled on the same process, model and stream directly after it: the same iterations
         # launched eagerly (identical kernels, arguments and shapes) with the library recording a pair of
@@ -327,7 +372,7 @@ def main():
         hold['cycles'] = 0
     _loop_stream.close()
     prof = []
-    if rank == 0 and not a.no_roofline and (eager_timed or runner.graphed):
+    if rank == 0 and roofline and (eager_timed or runner.graphed):
         import ctypes
         torch.cuda.synchronize()
         n = lib.rscotr_prof_pause()
@@ -380,7 +425,7 @@ def main():
         # dominant kernel of the step = the fp32 MFMA GEMM family; report the instantiation that takes the
         # most time, the whole family next to it
         gg = group('gemm')
-        pmc_applies = a.workload == 'mtl512' and a.size == WORKLOADS['mtl512']['size'] and a.batch == WORKLOADS['mtl512']['batch']
+        pmc_applies = roofline and a.workload == 'mtl512' and a.size == WORKLOADS['mtl512']['size'] and a.batch == WORKLOADS['mtl512']['batch']
         # (the fused attention core reports through the GEMM kind with DENSE-equivalent flops — fully masked tiles are skipped by
         # the kernel — and has its own two lines below: it stays out of the GEMM family's sums)
         ga = {k: v for k, v in gg.items() if 'attn_' in k}
@@ -525,16 +570,17 @@ def main():
                                rccl_ranks=dist.get_world_size() if dist.is_initialized() else 0,
                                exchange=(('inline' if os.environ.get('RSCOTR_DIST_INLINE', '1') != '0' else 'overlap')
                                          if dist.is_initialized() else None),
-                               hipgraph_tasks=list(runner.graphed.keys())),
-                   roofline=r_gemm, roofline_gemm_family=fam, roofline_msda_fwd=r_f, roofline_msda_bwd=r_b,
-                   roofline_attn_fwd=r_af, roofline_attn_bwd=r_ab, roofline_swin_wattn=r_wa, roofline_layernorm=r_ln,
-                   roofline_splitk=r_sk, roofline_adamw=r_ad, roofline_ffn=r_ffn,
-                   roofline_bracket_us=round(bracket_s * 1e6, 3),  # median empty event bracket, subtracted from every roofline sample
-                   per_task_ms=per_task)  # rank 0, device time per iteration inside the timed region
-        if world == 1 and not a.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(a.size, a.batch, a.cpu_rounds, a.workload)
-        else:
-            out['cpu_baseline'] = None
+                               hipgraph_tasks=list(runner.graphed.keys())))
+        if a.full:
+            out.update(roofline=r_gemm, roofline_gemm_family=fam, roofline_msda_fwd=r_f, roofline_msda_bwd=r_b,
+                       roofline_attn_fwd=r_af, roofline_attn_bwd=r_ab, roofline_swin_wattn=r_wa, roofline_layernorm=r_ln,
+                       roofline_splitk=r_sk, roofline_adamw=r_ad, roofline_ffn=r_ffn,
+                       roofline_bracket_us=round(bracket_s * 1e6, 3),  # median empty event bracket, subtracted from every roofline sample
+                       per_task_ms=per_task)  # rank 0, device time per iteration inside the timed region
+            if world == 1 and not a.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline(a.size, a.batch, a.cpu_rounds, a.workload)
+            else:
+                out['cpu_baseline'] = None
         os.write(json_fd, (json.dumps(out) + '\n').encode())
     if dist.is_initialized():
         dist.destroy_process_group()

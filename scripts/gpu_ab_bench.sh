@@ -7,7 +7,7 @@ mkdir -p $out
 i=0
 for envs in "$@"; do
   i=$((i+1))
-  env $envs python bench.py --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $out/v$i.json 2> $out/v$i.err
+  env $envs python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $out/v$i.json 2> $out/v$i.err
   python - "$out/v$i.json" "$envs" <<'PY'
 import json, sys
 try:

@@ -6,12 +6,13 @@
 # profiles/pmc_gemm_traffic.json, which bench.py reads for roofline.traffic.
 R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${1:-r1}
+OUT=${OUT:-$R/prof_out}; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$c
-  timeout 420 rocprofv3 --pmc $c --kernel-trace --kernel-include-regex 'gemm_f32_kernel|gemm_h3|ffn_h3|lin_h3|gemm_bf16x6|gemm_f32_group|msda_|attn_' --output-format csv -d /tmp/pmc_$c -o pmc -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --roofline-rounds 1 > $R/gpurun_out/${TAG}_pmc_$c.log 2>&1
+  timeout 420 rocprofv3 --pmc $c --kernel-trace --kernel-include-regex 'gemm_f32_kernel|gemm_h3|ffn_h3|lin_h3|gemm_bf16x6|gemm_f32_group|msda_|attn_' --output-format csv -d /tmp/pmc_$c -o pmc -- python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --roofline-rounds 1 > $OUT/${TAG}_pmc_$c.log 2>&1
   f=$(find /tmp/pmc_$c -name '*counter_collection.csv' | head -1)
-  python - "$f" "$R/gpurun_out/${TAG}_pmc_$c.csv" <<'PY'
+  python - "$f" "$OUT/${TAG}_pmc_$c.csv" <<'PY'
 import csv, sys, collections
 src, dst = sys.argv[1], sys.argv[2]
 agg = collections.OrderedDict()
@@ -27,5 +28,5 @@ with open(dst, 'w') as fh:
     for (k, c), (n, s) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
         w.writerow([k, c, n, s, s / n])
 PY
-  tail -2 $R/gpurun_out/${TAG}_pmc_$c.log | cut -c1-300 > $R/gpurun_out/${TAG}_pmc_$c.tail; rm $R/gpurun_out/${TAG}_pmc_$c.log
+  tail -2 $OUT/${TAG}_pmc_$c.log | cut -c1-300 > $OUT/${TAG}_pmc_$c.tail; rm $OUT/${TAG}_pmc_$c.log
 done

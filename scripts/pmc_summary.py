@@ -36,7 +36,7 @@ for k in fetch:
                           write_kib_per_launch=write[k][1] / write[k][0])
 json.dump({
     'command': "rocprofv3 --pmc <FETCH_SIZE|WRITE_SIZE> --kernel-trace --kernel-include-regex 'gemm_f32_kernel|gemm_h3|gemm_bf16x6|gemm_f32_group|msda_|attn_' -- python "
-               'bench.py --steps 1 --warmup 0 --no-cpu-baseline --roofline-rounds 1 (scripts/gpu_pmc.sh, scripts/pmc_summary.py)',
+               'bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --roofline-rounds 1 (scripts/gpu_pmc.sh, scripts/pmc_summary.py)',
     'units': 'KiB per dispatch as reported; FETCH_SIZE counts 128-B requests at 64 B on gfx950 (MI355X_MICROARCH.md, HBM): '
              'bench.py doubles it',
     'kernels': dict(sorted(kernels.items(), key=lambda kv: -kv[1]['dispatches'] * kv[1]['fetch_kib_per_launch'])),

@@ -43,3 +43,37 @@ def test_spawn_path_starts_the_ranks_and_prints_one_line(cuda):
     assert out['n_gpus'] == 1 and out['config']['rccl_ranks'] == 1 and out['config']['exchange'] == 'inline'
     assert out['config']['hipgraph_tasks'] == ['cls', 'det', 'seg'] and out['value'] > 0
     assert 'starting 1 rank(s)' in r.stderr
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(1200)
+def test_plain_run_and_dumped_outputs_repeat(cuda, tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line only — ms_per_step for exactly --steps timed steps, no
+    roofline / per-task / CPU-baseline fields — and --dump-outputs writes float .npy files under 64 MB in all.  Two runs
+    with the same arguments start from the same inputs, so what they dump is bitwise equal (the step is deterministic:
+    tests/test_determinism_gpu.py)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f'run{i}'
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                            '--size', '256', '--dump-outputs', str(d)], capture_output=True, text=True, timeout=550, env=_env())
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        out = json.loads(lines[0])
+        assert out['steps'] == 2 and out['ms_per_step'] > 0 and out['value'] > 0 and out['unit'] == 'images/s'
+        assert abs(out['value'] - 3 * 2 * 1000.0 / out['ms_per_step']) < 1e-6 * out['value']
+        assert not any(k.startswith('roofline') for k in out) and 'cpu_baseline' not in out and 'per_task_ms' not in out
+        files = sorted(p.name for p in d.iterdir())
+        assert 'params_sample.npy' in files and 'grads_sample.npy' in files
+        assert {f.split('.')[1] for f in files if f.startswith('log_vars.')} == {'cls', 'det', 'seg'}
+        arrs = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert np.abs(arrs['grads_sample.npy']).max() > 0
+        dumps.append(arrs)
+    a, b = dumps
+    assert a.keys() == b.keys()
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f
