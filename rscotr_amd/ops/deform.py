@@ -213,6 +213,11 @@ class _MSDAAttn(Function):
         v_is_x = value_in is None or value_in is x
         id_is_x = identity is x
         val2 = x2 if v_is_x else RANGES.carry(value_in, _f32c(value_in).reshape(-1, C))
+        if kpm is not None:
+            # padded tokens: the value projection reads them as zeros, so that what they hold reaches neither its operand's
+            # range word nor the rounding of the other rows (their rows of v are zeroed below); d(value_proj.weight) is
+            # unchanged, d(value) being 0 on them
+            val2 = val2.masked_fill(kpm.reshape(-1, 1), 0.0)
         Mk = val2.shape[0]
         Nk = Mk // B
         ws = [w if w.is_contiguous() else w.contiguous() for w in (w_off, w_aw, w_v, w_o)]

@@ -9,22 +9,34 @@ TASK_DATASET = dict(cls='resisc', det='dior', seg='potsdam')
 
 
 def make_batch(task, batch_size=2, size=512, seed=0, device='cpu', num_cls=45, num_det=20, num_seg=5,
-               max_gt=20):
+               max_gt=20, img_shapes=None):
+    """`size` is the canvas: an int (square) or an (H, W) tuple.  `img_shapes` (one (h, w) per image, h <= H, w <= W)
+    places each image in the top-left corner of the canvas, as mmdet's Pad does after Normalize: pixels outside it are 0,
+    its seg labels there are 255 (seg_pad_val), its det boxes lie inside it, and its metas carry img_shape = ori_shape =
+    (h, w, 3), pad_shape = (H, W, 3).  With an int size and no img_shapes the draws are those of a square, unpadded batch."""
+    H, W = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if img_shapes is None:
+        img_shapes = [(H, W)] * batch_size
+    img_shapes = [(int(h), int(w)) for h, w in img_shapes]
+    assert len(img_shapes) == batch_size and all(0 < h <= H and 0 < w <= W for h, w in img_shapes), (img_shapes, H, W)
     g = torch.Generator().manual_seed(seed)
     rs = np.random.RandomState(seed)
-    img = torch.randn(batch_size, 3, size, size, generator=g)
-    metas = [dict(img_shape=(size, size, 3), ori_shape=(size, size, 3), pad_shape=(size, size, 3),
-                  scale_factor=1.0, flip=False, filename=f'synthetic_{seed}_{i}') for i in range(batch_size)]
+    img = torch.randn(batch_size, 3, H, W, generator=g)
+    for i, (h, w) in enumerate(img_shapes):
+        img[i, :, h:, :] = 0
+        img[i, :, :, w:] = 0
+    metas = [dict(img_shape=(h, w, 3), ori_shape=(h, w, 3), pad_shape=(H, W, 3),
+                  scale_factor=1.0, flip=False, filename=f'synthetic_{seed}_{i}') for i, (h, w) in enumerate(img_shapes)]
     batch = dict(task=task, dataset_name=TASK_DATASET[task], img=img.to(device), img_metas=metas)
     if task == 'cls':
         batch['gt_label'] = torch.from_numpy(rs.randint(0, num_cls, batch_size)).long().to(device)
     elif task == 'det':
         boxes, labels, hboxes, hlabels = [], [], [], []
-        for _ in range(batch_size):
+        for h, w in img_shapes:
             G = int(rs.randint(1, max_gt + 1))
-            cxy = rs.uniform(0.1, 0.9, (G, 2)) * size
-            wh = rs.uniform(16, min(200, size / 2), (G, 2))
-            b = np.concatenate([cxy - wh / 2, cxy + wh / 2], 1).clip(0, size).astype(np.float32)
+            cxy = rs.uniform(0.1, 0.9, (G, 2)) * np.array([w, h])
+            wh = rs.uniform(16, min(200, min(h, w) / 2), (G, 2))
+            b = np.concatenate([cxy - wh / 2, cxy + wh / 2], 1).clip(0, np.array([w, h, w, h])).astype(np.float32)
             lab = rs.randint(0, num_det, G).astype(np.int64)
             boxes.append(torch.from_numpy(b).to(device))
             labels.append(torch.from_numpy(lab).to(device))
@@ -35,10 +47,13 @@ def make_batch(task, batch_size=2, size=512, seed=0, device='cpu', num_cls=45, n
         # them: DetStatic checks them against the device tensors' shapes)
         batch['gt_bboxes_host'], batch['gt_labels_host'] = hboxes, hlabels
     elif task == 'seg':
-        blk = 32 if size >= 64 else 8
-        coarse = rs.randint(0, num_seg, (batch_size, 1, (size + blk - 1) // blk, (size + blk - 1) // blk))
-        lab = np.kron(coarse, np.ones((1, 1, blk, blk), dtype=np.int64))[:, :, :size, :size]
+        blk = 32 if min(H, W) >= 64 else 8
+        coarse = rs.randint(0, num_seg, (batch_size, 1, (H + blk - 1) // blk, (W + blk - 1) // blk))
+        lab = np.kron(coarse, np.ones((1, 1, blk, blk), dtype=np.int64))[:, :, :H, :W]
         lab[rs.uniform(size=lab.shape) < 0.02] = 255
+        for i, (h, w) in enumerate(img_shapes):
+            lab[i, :, h:, :] = 255
+            lab[i, :, :, w:] = 255
         batch['gt_semantic_seg'] = torch.from_numpy(lab).long().to(device)
     else:
         raise ValueError(task)

@@ -184,3 +184,73 @@ def test_inference_path_matches_oracle_cpu(tiny, monkeypatch):
         assert float((np.stack(out) == ref.numpy()).mean()) >= 0.99
     finally:
         model.train()
+
+
+# padded det batches and non-square canvases (synth.make_batch(size=(H, W), img_shapes=...)): the head's masked route —
+# per-image masks and their sine encodings, key padding masks, valid ratios below 1, +inf proposals on padded tokens,
+# per-level 4-d decoder references — and W / H kept apart wherever levels are assembled
+PADDED_DET = dict(size=(64, 96), img_shapes=[(64, 70), (50, 96)])
+
+
+@pytest.mark.parametrize('task', ['cls', 'det', 'seg'])
+def test_train_step_non_square_and_padded_matches_oracle(tiny, task, monkeypatch):
+    patch_ops_with_oracle(monkeypatch)
+    mcfg, model = tiny
+    kw = PADDED_DET if task == 'det' else dict(size=(64, 96))
+    out, oout, rec, orec, P = run_step_pair(model, mcfg, task, seed=3, **kw)
+    check_step_pair(model, out, oout, rec, orec, P)
+
+
+def test_det_static_path_equals_dynamic_path_padded(tiny, monkeypatch):
+    """test_det_static_path_equals_dynamic_path on a padded, non-square batch: the static targets take each image's own
+    (w, h) factors."""
+    patch_ops_with_oracle(monkeypatch)
+    mcfg, model = tiny
+    from rscotr_amd import synth
+    batch = synth.make_batch('det', 2, seed=8, **PADDED_DET)
+    rnd = synth.make_rnd(model, batch, seed=8)
+    res = {}
+    for mode in (True, False):
+        model.bbox_head.static_path = mode
+        try:
+            model.zero_grad(set_to_none=True)
+            rec = {}
+            out = model.train_step(dict(batch, rnd=rnd, record=rec))
+            out['loss'].backward()
+            res[mode] = (out, rec, {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None})
+        finally:
+            model.bbox_head.static_path = True
+    (o1, r1, g1), (o2, r2, g2) = res[True], res[False]
+    assert list(o1['log_vars']) == list(o2['log_vars'])
+    for k, v in o1['log_vars'].items():
+        assert abs(v - o2['log_vars'][k]) <= 1e-5 * max(abs(v), 1e-3), k
+    assert r1['match'].keys() == r2['match'].keys()
+    for k in r1['match']:
+        assert (r1['match'][k][0] == r2['match'][k][0]).all() and (r1['match'][k][1] == r2['match'][k][1]).all()
+    assert g1.keys() == g2.keys()
+    for n in g1:
+        assert float((g1[n] - g2[n]).abs().max()) <= 1e-5 * max(float(g2[n].abs().max()), 1e-6) + 1e-7, n
+
+
+def test_padded_det_inference_matches_oracle_cpu(tiny, monkeypatch):
+    """simple_test_det on a padded batch with rescale=True: every image's boxes clamped to its own img_shape / scale_factor."""
+    import numpy as np
+    from oracle import model as OM
+    from rscotr_amd import synth
+    from util import state_to_oracle
+    patch_ops_with_oracle(monkeypatch)
+    mcfg, model = tiny
+    model.eval()
+    try:
+        P = state_to_oracle(model)
+        b = synth.make_batch('det', 2, seed=4, **PADDED_DET)
+        metas = [dict(m, scale_factor=np.array([0.5, 0.625, 0.5, 0.625], dtype=np.float32)) for m in b['img_metas']]
+        out = model(task='det', img=b['img'], img_metas=[dict(m) for m in metas], return_loss=False, rescale=True)
+        ref = OM.simple_test(P, mcfg, 'det', b['img'], metas, rescale=True)
+        for res, (rb, rl), m in zip(out, ref, metas):
+            got = np.concatenate(res, 0)
+            h, w = m['img_shape'][:2]
+            assert np.allclose(np.sort(got[:, 4]), np.sort(rb[:, 4].detach().numpy()), rtol=1e-4, atol=1e-6)
+            assert (got[:, [0, 2]] <= w / 0.5 + 1e-3).all() and (got[:, [1, 3]] <= h / 0.625 + 1e-3).all()
+    finally:
+        model.train()

@@ -282,3 +282,206 @@ def test_fused_prologue_equals_the_kernel_pair(cuda, refdim, packed, Nq):
     loc1, attn1, out1 = deform._msda_fwd_prep_raw(value, ss, lsi, off, logit, ref, norm, L, P, ldo, ldl)
     assert torch.equal(loc0, loc1) and torch.equal(attn0, attn1) and torch.equal(out0, out1)
     assert float(out1.abs().max()) > 0
+
+
+# ---- key padding masks and per-level 4-d references: the padded det batch (img_shape < batch_input_shape) -------------
+def _level_kpm(canvas, img_shapes, shapes):
+    """(B, Nk) bool, True on padded tokens: a per-image pixel mask, nearest-interpolated to each level as
+    DINOHead.forward does it."""
+    m = torch.ones((len(img_shapes),) + tuple(canvas))
+    for i, (h, w) in enumerate(img_shapes):
+        m[i, :h, :w] = 0
+    return torch.cat([torch.nn.functional.interpolate(m[None], size=s).to(torch.bool).squeeze(0).flatten(1)
+                      for s in shapes], 1)
+
+
+def _valid_ratios(kpm, shapes):
+    """(B, L, 2): the valid share (w, h) of every level, as get_valid_ratio reads it off the masks."""
+    out, s = [], 0
+    for h, w in shapes:
+        m = ~kpm[:, s:s + h * w].view(-1, h, w)
+        s += h * w
+        out.append(torch.stack([m[:, 0].sum(1) / w, m[:, :, 0].sum(1) / h], -1))
+    return torch.stack(out, 1).float()
+
+
+KPM_CASES = {
+    # the 512^2 pyramid, one image valid over 512 x 384 (B = 1), and the same image next to an unpadded one
+    'p512': ((512, 512), [(512, 384)], SHAPES_512),
+    'p512_mixed': ((512, 512), [(512, 512), (512, 384)], SHAPES_512),
+    # a ragged, non-square pyramid (stride 8 of a 120 x 88 canvas), mixed again
+    'ragged': ((120, 88), [(120, 88), (70, 41)], [(15, 11), (8, 6), (4, 3), (2, 2)]),
+}
+_KPM_REF = {}
+
+
+def _kpm_problem(case, kind):
+    canvas, img_shapes, shapes = KPM_CASES[case]
+    g = torch.Generator().manual_seed(len(case) * 7 + len(kind))
+    B, H, L, P, C = len(img_shapes), 8, 4, 4, 256
+    Nk = sum(h * w for h, w in shapes)
+    Nq = Nk if kind == 'encoder' else 150
+    kpm = _level_kpm(canvas, img_shapes, shapes)
+    assert kpm.any() and not kpm.all(1).any()
+    # valid ratios (w, h) per image and level, as get_valid_ratio: references scaled by them (encoder) or boxes scaled
+    # per level (decoder, unit_ratios=False)
+    vr = _valid_ratios(kpm, shapes)                                                                    # (B, L, 2)
+    if kind == 'encoder':
+        ref = torch.rand(B, Nq, 1, 2, generator=g) * vr[:, None, :, :]                                 # (B, Nq, L, 2)
+    else:
+        box = torch.cat([torch.rand(B, Nq, 1, 2, generator=g) * 0.8 + 0.1, torch.rand(B, Nq, 1, 2, generator=g) * 0.5 + 0.05], -1)
+        ref = box * torch.cat([vr, vr], -1)[:, None]                                                   # (B, Nq, L, 4)
+    mk = lambda *s, sc=1.0: torch.randn(*s, generator=g) * sc
+    W = dict(w_off=mk(H * L * P * 2, C, sc=0.02), b_off=mk(H * L * P * 2), w_aw=mk(H * L * P, C, sc=0.05), b_aw=mk(H * L * P, sc=0.1),
+             w_v=mk(C, C, sc=0.06), b_v=mk(C, sc=0.1), w_o=mk(C, C, sc=0.06), b_o=mk(C, sc=0.1))
+    x, pos, mem, gy = mk(B, Nq, C), mk(B, Nq, C), mk(B, Nk, C), mk(B, Nq, C)
+    return dict(shapes=shapes, kpm=kpm, ref=ref, W=W, x=x, pos=pos, mem=mem, gy=gy, H=H, L=L, P=P)
+
+
+def _kpm_oracle(case, kind):
+    """The oracle's msda_module (mmcv MultiScaleDeformableAttention.forward) in float64: output and every gradient."""
+    key = (case, kind)
+    if key not in _KPM_REF:
+        from oracle import model as OM
+        pb = _kpm_problem(case, kind)
+        names = dict(w_off='sampling_offsets.weight', b_off='sampling_offsets.bias', w_aw='attention_weights.weight',
+                     b_aw='attention_weights.bias', w_v='value_proj.weight', b_v='value_proj.bias', w_o='output_proj.weight',
+                     b_o='output_proj.bias')
+        Wd = {k: v.double().requires_grad_(True) for k, v in pb['W'].items()}
+        P64 = {'a.' + names[k]: v for k, v in Wd.items()}
+        x, pos, mem = (pb[k].double().requires_grad_(True) for k in ('x', 'pos', 'mem'))
+        shapes = pb['shapes']
+        lsi = [0] + [int(s) for s in torch.tensor([h * w for h, w in shapes]).cumsum(0)[:-1]]
+        y = OM.msda_module(x.transpose(0, 1), None if kind == 'encoder' else mem.transpose(0, 1), None, pos.transpose(0, 1),
+                           pb['kpm'], pb['ref'].double(), shapes, lsi, P64, 'a', heads=pb['H'], levels=pb['L'],
+                           points=pb['P']).transpose(0, 1)
+        y.backward(pb['gy'].double())
+        _KPM_REF[key] = dict(y=y.detach(), x=x.grad, pos=pos.grad, mem=None if kind == 'encoder' else mem.grad,
+                             **{k: v.grad for k, v in Wd.items()})
+    return _KPM_REF[key]
+
+
+def _kpm_product(pb, kind, cuda, mem_override=None):
+    from rscotr_amd import ops
+    ss = torch.tensor(pb['shapes'], dtype=torch.int64, device=cuda)
+    lsi = torch.cat([ss.new_zeros(1), (ss[:, 0] * ss[:, 1]).cumsum(0)[:-1]])
+    norm = torch.stack([ss[:, 1], ss[:, 0]], -1).float()
+    x, pos = (pb[k].to(cuda).requires_grad_(True) for k in ('x', 'pos'))
+    mem = (pb['mem'] if mem_override is None else mem_override).to(cuda).requires_grad_(True)
+    Wp = {k: v.to(cuda).requires_grad_(True) for k, v in pb['W'].items()}
+    value = x if kind == 'encoder' else mem
+    y = ops.msda_attention(x, pos, value, x, pb['kpm'].to(cuda), pb['ref'].to(cuda), ss, lsi, norm, pb['H'], pb['L'], pb['P'],
+                           Wp['w_off'], Wp['b_off'], Wp['w_aw'], Wp['b_aw'], Wp['w_v'], Wp['b_v'], Wp['w_o'], Wp['b_o'])
+    y.backward(pb['gy'].to(cuda))
+    torch.cuda.synchronize()
+    return dict(y=y.detach(), x=x.grad, pos=pos.grad, mem=None if kind == 'encoder' else mem.grad,
+                **{k: v.grad for k, v in Wp.items()})
+
+
+@pytest.mark.parametrize('kind', ['encoder', 'decoder'])
+@pytest.mark.parametrize('case', sorted(KPM_CASES))
+def test_msda_attention_key_padding_mask_matches_fp64(cuda, case, kind):
+    """ops.msda_attention with a key_padding_mask (padded det batches: every encoder and decoder MSDA node) against the
+    oracle's msda_module in float64 — output, d(x), d(query_pos), d(memory) and all 8 parameter gradients; masks as the
+    head builds them, references scaled by each image's valid ratios.  Exact: the output does not see what the masked
+    value rows hold, and d(memory) is exactly 0 on them."""
+    pb = _kpm_problem(case, kind)
+    ref = _kpm_oracle(case, kind)
+    got = _kpm_product(pb, kind, cuda)
+    for k, r in ref.items():
+        if r is None:
+            assert got[k] is None
+            continue
+        g = got[k].cpu().double()
+        assert torch.isfinite(g).all(), (case, kind, k)
+        d, tol = (g - r).abs(), 1e-3 * float(r.abs().max()) + 1e-6
+        if k in ('x', 'pos', 'w_off', 'b_off'):
+            # d(sampling offsets) is discontinuous where a sample crosses a cell boundary of the bilinear interpolation: a
+            # sample within fp32 rounding of one is a coin toss between fp32 and fp64 (measured: 1 row of d(query_pos) at
+            # 3.4e-3 of its maximum, p512_mixed).  Those tensors hold 1e-3 on 99.9 % of their elements, 1e-2 on all, 1e-4 in L2
+            rel_l2 = float(d.norm() / r.norm())
+            assert float((d > tol).double().mean()) <= 1e-3 and float(d.max()) <= 10 * tol and rel_l2 <= 1e-4, \
+                (case, kind, k, float(d.max()), float(r.abs().max()), int((d > tol).sum()), rel_l2)
+        else:
+            assert float(d.max()) <= tol, (case, kind, k, float(d.max()), float(r.abs().max()))
+    kpm = pb['kpm']
+    if kind == 'decoder':
+        assert bool((got['mem'].cpu()[kpm] == 0).all()), (case, float(got['mem'].cpu()[kpm].abs().max()))
+        junk = pb['mem'].clone()
+        junk[kpm] = torch.where(torch.rand(junk[kpm].shape, generator=torch.Generator().manual_seed(1)) < 0.5, -1e4, 1e4)
+        again = _kpm_product(pb, kind, cuda, mem_override=junk)
+        assert torch.equal(again['y'], got['y']), (case, float((again['y'] - got['y']).abs().max()))
+        assert torch.equal(again['x'], got['x']) and bool((again['mem'].cpu()[kpm] == 0).all())
+
+
+def _box_refs(B, Nq, L, g):
+    """(B, Nq, L, 4) per-level boxes: one box per query scaled by per-level valid ratios in (0.1, 1] (the decoder's
+    reference_points[:, :, None] * cat([valid_ratios, valid_ratios], -1)[:, None])."""
+    box = torch.cat([torch.rand((B, Nq, 1, 2), generator=g) * 0.8 + 0.1, torch.rand((B, Nq, 1, 2), generator=g) * 0.6 + 0.05], -1)
+    vr = torch.rand((B, 1, L, 2), generator=g) * 0.9 + 0.1
+    return box * torch.cat([vr, vr], -1)
+
+
+@pytest.mark.parametrize('packed', [True, False])
+@pytest.mark.parametrize('Nq', [1100, 37])
+def test_fused_prologue_per_level_boxes(cuda, packed, Nq):
+    """rscotr_msda_fwd_prep in its ref_levels == L, refdim == 4 mode (decoder of a padded batch) against
+    rscotr_msda_prep_fwd + rscotr_msda_fwd bit for bit, and loc against xy + off / P * wh * 0.5 in float64; offsets large
+    enough that many samples leave the map."""
+    from rscotr_amd.ops import deform
+    shapes = [(64, 64), (32, 32), (16, 16), (8, 8)]
+    B, H, D, L, P = 2, 8, 32, 4, 4
+    Nk = sum(h * w for h, w in shapes)
+    g = torch.Generator().manual_seed(Nq + 4)
+    ss = torch.tensor(shapes, dtype=torch.long, device=cuda)
+    lsi = torch.tensor([0, 4096, 5120, 5376], dtype=torch.long, device=cuda)
+    value = torch.randn((B, Nk, H, D), generator=g).to(cuda)
+    n = H * L * P
+    both_h = torch.randn((B * Nq, 3 * n), generator=g) * 8.0
+    both = both_h.to(cuda)
+    if packed:
+        off, logit, ldo, ldl = both, both.view(-1)[2 * n:], 3 * n, 3 * n
+    else:
+        off, logit, ldo, ldl = both[:, :2 * n].contiguous(), both[:, 2 * n:].contiguous(), 2 * n, n
+    ref_h = _box_refs(B, Nq, L, g)
+    ref = ref_h.to(cuda)
+    assert deform._msda_fused_ok(Nk, H, D, L, P)
+    loc0, attn0 = deform._msda_prep_fwd_raw(off, logit, ref, None, B, Nq, H, L, P, ld_off=ldo, ld_logit=ldl)
+    out0 = deform._msda_fwd_raw(value, ss, lsi, loc0, attn0)
+    loc1, attn1, out1 = deform._msda_fwd_prep_raw(value, ss, lsi, off, logit, ref, None, L, P, ldo, ldl)
+    assert torch.equal(loc0, loc1) and torch.equal(attn0, attn1) and torch.equal(out0, out1)
+    assert float(out1.abs().max()) > 0
+    o6 = both_h[:, :2 * n].double().view(B, Nq, H, L, P, 2)
+    r = ref_h.double()
+    loc_r = r[:, :, None, :, None, :2] + o6 / P * r[:, :, None, :, None, 2:] * 0.5
+    outside = ((loc_r < 0) | (loc_r > 1)).any(-1).double().mean()
+    assert 0.05 < float(outside) < 0.95, float(outside)
+    assert float((loc1.cpu().double() - loc_r).abs().max()) <= 1e-6 * float(loc_r.abs().max())
+    aw_r = both_h[:, 2 * n:].double().view(B, Nq, H, L * P).softmax(-1).view(B, Nq, H, L, P)
+    assert float((attn1.cpu().double() - aw_r).abs().max()) <= 1e-6
+
+
+@pytest.mark.parametrize('packed', [True, False])
+def test_prep_bwd_per_level_boxes_matches_autograd(cuda, packed):
+    """_msda_prep_bwd_raw with refdim == 4, ref_levels == L (packed and unpacked gradient layouts) against torch autograd
+    of the same formula in float64."""
+    from rscotr_amd.ops import deform
+    B, Nq, H, L, P = 2, 53, 8, 4, 4
+    g = torch.Generator().manual_seed(91)
+    n = H * L * P
+    off = torch.randn(B, Nq, 2 * n, generator=g) * 8.0
+    logit = torch.randn(B, Nq, H, L * P, generator=g) * 2.0
+    ref = _box_refs(B, Nq, L, g)
+    gl = torch.randn(B, Nq, H, L, P, 2, generator=g)
+    ga = torch.randn(B, Nq, H, L, P, generator=g)
+    o, lg, r = off.double().requires_grad_(True), logit.double().requires_grad_(True), ref.double()
+    loc_r = r[:, :, None, :, None, :2] + o.view(B, Nq, H, L, P, 2) / P * r[:, :, None, :, None, 2:] * 0.5
+    aw_r = lg.softmax(-1).view(B, Nq, H, L, P)
+    ((loc_r * gl.double()).sum() + (aw_r * ga.double()).sum()).backward()
+    attn = aw_r.detach().float().to(cuda).contiguous()
+    goff, glogit = deform._msda_prep_bwd_raw(gl.to(cuda), ga.to(cuda), attn, ref.to(cuda), None, B, Nq, H, L, P, packed=packed)
+    if packed:
+        goff, glogit = goff[:, :2 * n], goff[:, 2 * n:]
+    goff, glogit = goff.reshape(B, Nq, 2 * n).cpu().double(), glogit.reshape(B, Nq, H, L * P).cpu().double()
+    rel = lambda a, b: float((a - b).abs().max() / (b.abs().max() + 1e-30))
+    assert rel(goff, o.grad) < 1e-5 and rel(glogit, lg.grad) < 1e-5, (rel(goff, o.grad), rel(glogit, lg.grad))
