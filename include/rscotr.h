@@ -29,9 +29,9 @@ extern "C" {
 
 /* ABI revision: bumped whenever an exported entry changes its argument list (round 5 inserted amax_out / nbytes before
  * `stream` in the LayerNorm, window-attention, MSDA backward, pack4, splitk_flush and grouped-dW entries = revision 6;
- * round 6 = 7).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
+ * round 6 = 7; 11 added the resampling input entries rscotr_img_aug_u8 / rscotr_seg_label_aug_u8).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
  * its first call (rscotr_amd/_lib.py does) — a stale .so would take a stream handle for a pointer. */
-#define RSCOTR_ABI_VERSION 10
+#define RSCOTR_ABI_VERSION 11
 int rscotr_version(void);
 const char* rscotr_last_error(void);
 int rscotr_device_count(void);
@@ -679,6 +679,29 @@ int rscotr_img_prep_u8(const uint8_t* src, const int64_t* meta, float* out, int 
                        const float* mean3, const float* std3, int to_rgb, void* stream);
 int rscotr_seg_label_prep_u8(const uint8_t* src, const int64_t* meta, int64_t* out, int B, int Hout, int Wout,
                              int reduce_zero_label, int pad_val, void* stream);
+
+/* rscotr_img_aug_u8: the same collate with a RESIZED frame and the colour stages in front of Normalize, one launch per batch:
+ * pad test -> flip of the output index -> window into the resized frame -> resample from the raw uint8 source ->
+ * PhotoMetricDistortion (mmseg 0.28, per pixel on the uint8 BGR triplet) -> RandomErasing patch -> normalize -> CHW float32.
+ * Replaces mmcv imresize / imrescale (cv2 'bilinear' | 'nearest', pillow 'bicubic'), mmseg Resize / PhotoMetricDistortion,
+ * mmcls RandomResizedCrop / Resize / RandomErasing, mmdet Resize of configs/_base_/cls/resisc_swin_224.py:10-14,28-35,43-48,
+ * configs/_base_/det/dior.py:13, configs/_base_/seg/potsdam_IRRG_all.py:10,14.
+ * meta: device (B, 20) int64 rows {byte offset, H, W, row stride in bytes, out w, out h, flip, x-table offset, y-table offset
+ * (int32 elements into `tables`), x taps K, y taps K, resample mode (0 nearest, 1 OpenCV fixed-point bilinear, 2 Pillow
+ * bicubic), photometric flags (1 brightness, 2 contrast, 4 contrast before saturation, 8 saturation, 16 hue; 0 = off),
+ * hue delta, erase x0, erase y0, erase w, erase h (0 = off), erase patch byte offset into src (HWC uint8 BGR), reserved}.
+ * tables: device int32; per sample and axis, one entry of K + 2 words per output coordinate {first source index, taps n <= K,
+ * n integer weights}; the window's offset into the resized frame is folded into the entries.  The host builds them
+ * (rscotr_amd/pipeline.py), so the arithmetic is exact: bilinear = (sum wy * sum wx * p + 2^21) >> 22 with 11-bit weights,
+ * bicubic = Pillow's 22-bit two-pass form with its uint8 intermediate.  Every index must lie inside its source and
+ * out w / h <= Wout / Hout (caller-checked).  params: device (B, 4) float {brightness beta, contrast alpha, saturation
+ * alpha, reserved}.  With resample 0 over identity entries and every stage off the result equals rscotr_img_prep_u8's.
+ * rscotr_seg_label_aug_u8: the same geometry for a label map through nearest entries (meta / tables of the same layout),
+ * then reduce_zero_label, then pad_val. */
+int rscotr_img_aug_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, const float* params, float* out,
+                      int B, int Hout, int Wout, const float* mean3, const float* std3, int to_rgb, void* stream);
+int rscotr_seg_label_aug_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, int64_t* out, int B, int Hout,
+                            int Wout, int reduce_zero_label, int pad_val, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,11 +4,22 @@ the three datasets' on-disk layouts.
 
 Reference pipelines (configs/_base_/cls/resisc_swin_224.py:7-39, configs/_base_/det/dior.py:11-20,
 configs/_base_/seg/potsdam_IRRG_all.py:8-19):
-    decode -> [resize / RandAugment / PhotoMetricDistortion: host, not here] -> RandomCrop window (seg)
-           -> RandomFlip -> Normalize(mean, std, to_rgb) -> Pad -> ImageToTensor / DefaultFormatBundle -> collate.
+    decode (host) -> [Resize / RandomResizedCrop] -> RandomCrop window (seg) -> RandomFlip -> [PhotoMetricDistortion]
+           -> [RandomErasing] -> Normalize(mean, std, to_rgb) -> Pad -> ImageToTensor / DefaultFormatBundle -> collate
+(bracketed: the optional stages below; RandAugment is not implemented).
 Everything from the crop window on runs on the device; the host only draws the random decisions (with the same NumPy
 calls and in the same order as the mm* transforms, so a seeded run makes the same decisions) and uploads the raw bytes
 through one pinned staging buffer.  There is no CPU fallback: without the HIP library `collate` raises.
+
+Optional stages (`resize=`, `random_resized_crop=`, `photometric=`, `random_erasing=`; all off by default, and then the
+collate is exactly the crop / flip / normalize / pad launch above) move the resampling and colour steps onto the device as
+well: one `rscotr_img_aug_u8` launch per batch.  The host draws their random decisions and builds per-axis resampling
+tables (source index, tap count and integer weights per output coordinate), so the device arithmetic is integer and exact:
+  'cv2'     mmcv imresize / imrescale interpolation='bilinear': the scalar fixed-point form of OpenCV's uint8 INTER_LINEAR
+            (11-bit weights).  Parity with cv2 itself is unpinned: +-1 LSB expected (SIMD / IPP / exact-2x paths), unmeasured.
+  'pillow'  mmcv backend='pillow', interpolation='bicubic': Pillow's ImagingResample (antialiased, 22-bit weights,
+            uint8-clipped horizontal pass then vertical pass); equal to Pillow's own output.
+Label maps are resampled 'nearest' (mmcv: cv2 INTER_NEAREST).  RandAugment is not implemented (`build_collate`).
 """
 import ctypes
 import json
@@ -22,6 +33,13 @@ from . import ops
 
 IMG_NORM = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
 META = 10
+AUG_META, AUG_PARAMS = 20, 4  # include/rscotr.h: rscotr_img_aug_u8's meta row and params row
+RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_PIL = 0, 1, 2
+PM_BRIGHT, PM_CONTRAST, PM_CONTRAST_FIRST, PM_SAT, PM_HUE = 1, 2, 4, 8, 16
+PHOTOMETRIC = dict(brightness_delta=32, contrast_range=(0.5, 1.5), saturation_range=(0.5, 1.5), hue_delta=18)
+RANDOM_ERASING = dict(erase_prob=0.5, min_area_ratio=0.02, max_area_ratio=0.4, aspect_range=(3 / 10, 10 / 3), mode='const',
+                      fill_color=(128, 128, 128), fill_std=None)  # mmcls RandomErasing's defaults
+RANDOM_RESIZED_CROP = dict(size=224, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.), max_attempts=10)
 
 
 def _host_floats(v):
@@ -33,13 +51,98 @@ def _round_up(x, d):
     return (x + d - 1) // d * d
 
 
+# ---- per-axis resampling tables: entry j (output coordinate o0 + j of an axis resized n_in -> n_out, whose source starts at
+# src0) = {first source index, taps n, n weights}, int32 rows of K + 2 words ------------------------------------------------
+def _table(first, n, w):
+    K = max(int(w.shape[1]), 1)
+    t = np.zeros((len(first), K + 2), np.int32)
+    t[:, 0], t[:, 1] = first, n
+    t[:, 2:2 + w.shape[1]] = w
+    return t
+
+
+def _axis_nearest(n_in, n_out, src0, o0, count):
+    """cv2 INTER_NEAREST (mmcv 'nearest'): sx = min(floor(o * (1 / (n_out / n_in))), n_in - 1), in float64."""
+    o = np.arange(o0, o0 + count, dtype=np.float64)
+    s = np.minimum(np.floor(o * (1.0 / (n_out / n_in))).astype(np.int64), n_in - 1)
+    return _table(s + src0, np.ones(count, np.int64), np.zeros((count, 1), np.int32))
+
+
+def _axis_linear(n_in, n_out, src0, o0, count):
+    """cv2 INTER_LINEAR, uint8 fixed point: f = float32((o + 0.5) * scale - 0.5), s = floor(f), a = f - s; out-of-range
+    taps clamp to ONE tap of weight 2048; weights rint((1 - a) * 2048), rint(a * 2048) in float32 (saturate_cast<short>)."""
+    o = np.arange(o0, o0 + count, dtype=np.float64)
+    f = ((o + 0.5) * (1.0 / (n_out / n_in)) - 0.5).astype(np.float32)
+    s = np.floor(f).astype(np.int64)
+    a = (f - s.astype(np.float32)).astype(np.float32)
+    clamp = (s < 0) | (s >= n_in - 1)
+    s = np.where(s < 0, 0, np.where(s >= n_in - 1, n_in - 1, s))
+    a = np.where(clamp, np.float32(0), a).astype(np.float32)
+    w = np.stack([np.rint((np.float32(1) - a) * np.float32(2048)), np.rint(a * np.float32(2048))], -1).astype(np.int32)
+    w[clamp, 1] = 0
+    return _table(s + src0, np.where(clamp, 1, 2), w)
+
+
+def _bicubic(x):  # Pillow Resample.c bicubic_filter, a = -0.5
+    x = np.abs(x)
+    a = -0.5
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1,
+                    np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
+
+
+def _axis_pil_bicubic(n_in, n_out, src0, o0, count):
+    """Pillow precompute_coeffs + normalize_coeffs_8bpc for BICUBIC (support 2 * max(scale, 1)), coefficients normalised in
+    float64 (sequential sum, as the C loop), then 22-bit fixed point rounded away from zero."""
+    scale = n_in / n_out
+    fscale = max(scale, 1.0)
+    support = 2.0 * fscale
+    ksize = int(np.ceil(support)) * 2 + 1
+    center = (np.arange(o0, o0 + count, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    xmax = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), n_in) - xmin
+    t = np.arange(ksize)
+    live = t[None, :] < xmax[:, None]
+    k = np.where(live, _bicubic(((t[None, :] + xmin[:, None]) - center[:, None] + 0.5) * (1.0 / fscale)), 0.0)
+    ww = np.zeros(count)
+    for i in range(ksize):
+        ww = ww + k[:, i]
+    k = np.where(ww[:, None] != 0.0, k / np.where(ww == 0.0, 1.0, ww)[:, None], k)
+    w = np.where(k < 0, np.trunc(-0.5 + k * (1 << 22)), np.trunc(0.5 + k * (1 << 22))).astype(np.int32)
+    w[~live] = 0
+    return _table(xmin + src0, xmax, w)
+
+
+_AXIS = {RESAMPLE_NEAREST: _axis_nearest, RESAMPLE_LINEAR: _axis_linear, RESAMPLE_PIL: _axis_pil_bicubic}
+
+
+def _scale_size(w, h, scale):  # mmcv _scale_size
+    return int(w * float(scale) + 0.5), int(h * float(scale) + 0.5)
+
+
+def rescale_size(w, h, scale):
+    """mmcv rescale_size: a number, or a (long, short) edge pair -> ((new_w, new_h), scale factor)."""
+    if isinstance(scale, (float, int)):
+        sf = scale
+    else:
+        sf = min(max(scale) / max(h, w), min(scale) / min(h, w))
+    return _scale_size(w, h, sf), sf
+
+
 class DeviceCollate:
     """Batch builder for one task.  `__call__(samples, rng=None)` takes the decoded samples of one batch
     (dicts with `img`: HWC uint8 BGR ndarray, and per task `gt_label` | `gt_bboxes`, `gt_labels` | `gt_semantic_seg`:
     HW uint8) and returns the batch dict `MTL.train_step` consumes, tensors on `device`."""
 
     def __init__(self, task, device, img_norm_cfg=None, flip_prob=0.5, size_divisor=None, crop_size=None,
-                 cat_max_ratio=1.0, reduce_zero_label=False, seg_pad_val=255, ignore_index=255):
+                 cat_max_ratio=1.0, reduce_zero_label=False, seg_pad_val=255, ignore_index=255, resize=None,
+                 random_resized_crop=None, photometric=None, random_erasing=None, resize_backend='cv2'):
+        """Optional stages (None = off; any of them on routes the batch through `rscotr_img_aug_u8`):
+        resize: mmseg / mmdet Resize, dict(img_scale=(long, short), ratio_range=None | (lo, hi), keep_ratio=True), or
+                mmcls Resize, dict(size=(h, w)) (a fixed size);
+        random_resized_crop: mmcls RandomResizedCrop, dict(size, scale, ratio, max_attempts) (RANDOM_RESIZED_CROP);
+        photometric: mmseg PhotoMetricDistortion, True or dict (PHOTOMETRIC);
+        random_erasing: mmcls RandomErasing, dict (RANDOM_ERASING);
+        resize_backend: 'cv2' (bilinear) | 'pillow' (bicubic), the image resample of resize / random_resized_crop."""
         assert task in ('cls', 'det', 'seg')
         self.task, self.device = task, torch.device(device)
         cfg = dict(IMG_NORM if img_norm_cfg is None else img_norm_cfg)
@@ -48,11 +151,29 @@ class DeviceCollate:
         self.cat_max_ratio, self.reduce_zero_label = cat_max_ratio, reduce_zero_label
         self.seg_pad_val, self.ignore_index = seg_pad_val, ignore_index
         self._stage = None  # pinned byte staging buffer (grow-only)
+        if resize_backend not in ('cv2', 'pillow'):
+            raise ValueError(f'resize_backend must be cv2 (bilinear) or pillow (bicubic), not {resize_backend!r}')
+        if resize is not None and random_resized_crop is not None:
+            raise ValueError('resize and random_resized_crop are exclusive')
+        self.resize = None if resize is None else dict(dict(ratio_range=None, keep_ratio=True), **resize)
+        if self.resize is not None and ('size' in self.resize) == ('img_scale' in self.resize):
+            raise ValueError('resize takes img_scale=(long, short) (mmseg / mmdet) or size=(h, w) (mmcls)')
+        self.rrc = None if random_resized_crop is None else dict(RANDOM_RESIZED_CROP, **random_resized_crop)
+        self.photometric = None if not photometric else dict(PHOTOMETRIC, **(photometric if isinstance(photometric, dict)
+                                                                             else {}))
+        self.erasing = None if random_erasing is None else dict(RANDOM_ERASING, **random_erasing)
+        self.resample = RESAMPLE_PIL if resize_backend == 'pillow' else RESAMPLE_LINEAR
+        self.augmented = any(x is not None for x in (self.resize, self.rrc, self.photometric, self.erasing))
+        self.skipped = []  # transforms build_collate was told to skip
+        self._stage_done = None  # event after the last upload out of the staging buffer (augmented path)
 
     # ---- host-side random decisions (the draws of mmcv / mmseg / mmdet RandomFlip and mmseg RandomCrop) ----------
     def _crop_window(self, img, seg, rng):
         """mmseg RandomCrop.get_crop_bbox + the cat_max_ratio retry loop (up to 10 draws)."""
-        H, W = img.shape[:2]
+        return self._crop_window_hw(img.shape[0], img.shape[1], seg, rng)
+
+    def _crop_window_hw(self, H, W, seg, rng):
+        """The same on an (H, W) frame; `seg` = None, an (H, W) label map, or a function (x0, y0, w, h) -> label window."""
         ch, cw = self.crop_size
 
         def draw():
@@ -63,7 +184,7 @@ class DeviceCollate:
         if self.cat_max_ratio < 1.0 and seg is not None:
             for _ in range(10):
                 x0, y0, w, h = win
-                lab, cnt = np.unique(seg[y0:y0 + h, x0:x0 + w], return_counts=True)
+                lab, cnt = np.unique(seg(x0, y0, w, h) if callable(seg) else seg[y0:y0 + h, x0:x0 + w], return_counts=True)
                 # the reference counts on the label map AFTER LoadAnnotations: with reduce_zero_label the raw values 0
                 # and 255 are both the ignore index there
                 keep = ((lab != 0) & (lab != 255)) if self.reduce_zero_label else (lab != self.ignore_index)
@@ -86,8 +207,274 @@ class DeviceCollate:
             o += a.nbytes
         return self._stage[:total].to(self.device, non_blocking=True), offs
 
+    # ---- host-side draws of the optional stages -----------------------------------------------------------------------
+    def _rrc_params(self, H, W, rng):
+        """mmcls RandomResizedCrop.get_params -> (offset_h, offset_w, target_h, target_w)."""
+        import math
+        scale, ratio = self.rrc['scale'], self.rrc['ratio']
+        area = H * W
+        for _ in range(self.rrc['max_attempts']):
+            target_area = rng.uniform(*scale) * area
+            log_ratio = (math.log(ratio[0]), math.log(ratio[1]))
+            aspect_ratio = math.exp(rng.uniform(*log_ratio))
+            tw = int(round(math.sqrt(target_area * aspect_ratio)))
+            th = int(round(math.sqrt(target_area / aspect_ratio)))
+            if 0 < tw <= W and 0 < th <= H:
+                return rng.randint(0, H - th + 1), rng.randint(0, W - tw + 1), th, tw
+        in_ratio = float(W) / float(H)  # fallback: central crop
+        if in_ratio < min(ratio):
+            tw = W
+            th = int(round(tw / min(ratio)))
+        elif in_ratio > max(ratio):
+            th = H
+            tw = int(round(th * max(ratio)))
+        else:
+            tw, th = W, H
+        return (H - th) // 2, (W - tw) // 2, th, tw
+
+    def _resize_shape(self, H, W, rng):
+        """mmseg / mmdet Resize (random_sample_ratio, then mmcv rescale_size) or mmcls Resize -> (new_w, new_h)."""
+        r = self.resize
+        if 'size' in r:
+            return int(r['size'][1]), int(r['size'][0])
+        scale = tuple(r['img_scale'])
+        if r['ratio_range'] is not None:
+            lo, hi = r['ratio_range']
+            ratio = rng.random_sample() * (hi - lo) + lo
+            scale = int(scale[0] * ratio), int(scale[1] * ratio)
+        if r['keep_ratio']:
+            return rescale_size(W, H, scale)[0]
+        return int(scale[0]), int(scale[1])
+
+    def _photometric_draws(self, rng):
+        """mmseg PhotoMetricDistortion.__call__'s draws -> (flags, beta, contrast alpha, saturation alpha, hue delta)."""
+        p = self.photometric
+        flags, beta, ca, sa, hd = 0, 0.0, 1.0, 1.0, 0
+        if rng.randint(2):
+            flags |= PM_BRIGHT
+            beta = rng.uniform(-p['brightness_delta'], p['brightness_delta'])
+        mode = rng.randint(2)
+
+        def contrast():
+            if rng.randint(2):
+                return PM_CONTRAST, rng.uniform(*p['contrast_range'])
+            return 0, 1.0
+        if mode == 1:
+            f, ca = contrast()
+            flags |= f | (PM_CONTRAST_FIRST if f else 0)
+        if rng.randint(2):
+            flags |= PM_SAT
+            sa = rng.uniform(*p['saturation_range'])
+        if rng.randint(2):
+            flags |= PM_HUE
+            hd = rng.randint(-p['hue_delta'], p['hue_delta'])
+        if mode == 0:
+            f, ca = contrast()
+            flags |= f
+        return flags, beta, ca, sa, hd
+
+    def _erasing_draws(self, img_h, img_w, rng):
+        """mmcls RandomErasing.__call__ / _fill_pixels -> (left, top, w, h, HWC uint8 patch) or None."""
+        e = self.erasing
+        if rng.rand() > e['erase_prob']:
+            return None
+        log_aspect_range = np.log(np.array(e['aspect_range'], dtype=np.float32))
+        aspect_ratio = np.exp(rng.uniform(*log_aspect_range))
+        area = img_h * img_w
+        area *= rng.uniform(e['min_area_ratio'], e['max_area_ratio'])
+        h = min(int(round(np.sqrt(area * aspect_ratio))), img_h)
+        w = min(int(round(np.sqrt(area / aspect_ratio))), img_w)
+        top = rng.randint(0, img_h - h) if img_h > h else 0
+        left = rng.randint(0, img_w - w) if img_w > w else 0
+        if e['mode'] == 'const':
+            patch = np.empty((h, w, 3), dtype=np.uint8)
+            patch[:, :] = np.array(e['fill_color'], dtype=np.uint8)
+        elif e['fill_std'] is None:
+            patch = rng.uniform(0, 256, (h, w, 3)).astype(np.uint8)
+        else:
+            patch = rng.normal(e['fill_color'], e['fill_std'], (h, w, 3))
+            patch = np.clip(patch.astype(np.int32), 0, 255).astype(np.uint8)
+        return left, top, w, h, patch
+
+    def draw(self, img_shape, seg, rng):
+        """Every random decision of one sample, in the reference's order (geometry, crop, flip, photometric, erasing):
+        a dict with the source rectangle `src` (x, y, w, h), the resized frame `rsz` (w, h), the window `win` (x0, y0, w, h)
+        in that frame, `flip`, `pm` (photometric draws or None) and `erase` (or None)."""
+        H, W = img_shape[:2]
+        if self.rrc is not None:
+            oy, ox, th, tw = self._rrc_params(H, W, rng)
+            size = self.rrc['size']
+            sh, sw = (size, size) if isinstance(size, int) else size
+            src, rsz = (ox, oy, tw, th), (sw, sh)
+        elif self.resize is not None:
+            src, rsz = (0, 0, W, H), self._resize_shape(H, W, rng)
+        else:
+            src, rsz = (0, 0, W, H), (W, H)
+        if self.crop_size:
+            lab = None
+            if seg is not None and self.cat_max_ratio < 1.0:
+                if rsz == (W, H):
+                    lab = seg
+                else:  # the retries look at the nearest-resized label map, as the reference's RandomCrop does
+                    def lab(x0, y0, w, h):
+                        ys = _axis_nearest(H, rsz[1], 0, y0, h)[:, 0]
+                        xs = _axis_nearest(W, rsz[0], 0, x0, w)[:, 0]
+                        return seg[ys[:, None], xs[None, :]]
+            win = self._crop_window_hw(rsz[1], rsz[0], lab, rng)
+        else:
+            win = (0, 0, rsz[0], rsz[1])
+        d = dict(src=src, rsz=rsz, win=win, flip=bool(rng.rand() < self.flip_prob), pm=None, erase=None)
+        if self.photometric is not None:
+            d['pm'] = self._photometric_draws(rng)
+        if self.erasing is not None:
+            d['erase'] = self._erasing_draws(win[3], win[2], rng)
+        return d
+
+    def _upload(self, arrays):
+        """One host-to-device copy of `arrays` (16-byte aligned) out of the pinned staging buffer -> (device bytes, offsets).
+        The buffer is rewritten only after the previous copy out of it has completed."""
+        offs = self._upload_offsets(arrays)
+        total = max(_round_up(offs[-1] + arrays[-1].nbytes, 16), 16)
+        if self._stage_done is not None:
+            self._stage_done.synchronize()
+        if self._stage is None or self._stage.numel() < total:
+            self._stage = torch.empty(max(total, 1 << 20), dtype=torch.uint8, pin_memory=self.device.type == 'cuda')
+        view = self._stage.numpy()
+        for a, o in zip(arrays, offs):
+            view[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+        buf = self._stage[:total].to(self.device, non_blocking=True)
+        if self.device.type == 'cuda':
+            self._stage_done = torch.cuda.Event()
+            self._stage_done.record()
+        return buf, offs
+
+    def _call_augmented(self, samples, rng):
+        B = len(samples)
+        imgs = [s['img'] for s in samples]
+        segs = [s.get('gt_semantic_seg') for s in samples]
+        ds = []
+        for img, seg in zip(imgs, segs):
+            assert img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3, 'decoded HWC uint8 images expected'
+            ds.append(self.draw(img.shape, seg, rng))
+        if self.crop_size:
+            Hout, Wout = self.crop_size
+        else:
+            Hout, Wout = max([d['win'][3] for d in ds], default=0), max([d['win'][2] for d in ds], default=0)
+            if self.size_divisor:
+                Hout, Wout = _round_up(Hout, self.size_divisor), _round_up(Wout, self.size_divisor)
+        # per-axis tables (identity nearest entries where a sample is not resized: its window is read as is)
+        tabs, tab_off, n_tab = [], [], 0
+
+        def add(t):
+            nonlocal n_tab
+            tabs.append(t)
+            n_tab += t.size
+            return n_tab - t.size, t.shape[1] - 2
+        geo = []
+        for img, d in zip(imgs, ds):
+            (sx, sy, sw, sh), (rw, rh), (x0, y0, cw, ch) = d['src'], d['rsz'], d['win']
+            assert 0 <= x0 and 0 <= y0 and x0 + cw <= rw and y0 + ch <= rh and cw <= Wout and ch <= Hout
+            mode = RESAMPLE_NEAREST if (sw, sh) == (rw, rh) else self.resample
+            xt, kx = add(_AXIS[mode](sw, rw, sx, x0, cw))
+            yt, ky = add(_AXIS[mode](sh, rh, sy, y0, ch))
+            geo.append((mode, xt, kx, yt, ky))
+        lgeo = []
+        if self.task == 'seg':
+            for seg, d in zip(segs, ds):
+                (sx, sy, sw, sh), (rw, rh), (x0, y0, cw, ch) = d['src'], d['rsz'], d['win']
+                assert seg is not None and seg.shape[:2] == imgs[len(lgeo)].shape[:2]
+                xt, kx = add(_axis_nearest(sw, rw, sx, x0, cw))
+                yt, ky = add(_axis_nearest(sh, rh, sy, y0, ch))
+                lgeo.append((xt, kx, yt, ky))
+        tables = np.concatenate([t.reshape(-1) for t in tabs]) if tabs else np.zeros(1, np.int32)
+        # bounds of every source read (the kernel cannot check them)
+        for t, dim in zip(tabs[:2 * B], [n for im in imgs for n in (im.shape[1], im.shape[0])]):
+            assert (t[:, 0] >= 0).all() and (t[:, 0] + t[:, 1] <= dim).all() and (t[:, 1] >= 1).all()
+        patches = [d['erase'][4] for d in ds if d['erase'] is not None]
+        params = np.zeros((max(B, 1), AUG_PARAMS), np.float32)
+        for b, d in enumerate(ds):
+            if d['pm'] is not None:
+                params[b, :3] = d['pm'][1:4]
+        nimg = len(imgs)
+        lsegs = [np.ascontiguousarray(sg) for sg in segs] if self.task == 'seg' else []
+        # layout of the one upload: images | label maps | erasing patches | tables | params | meta | label meta
+        meta = np.zeros((max(B, 1), AUG_META), np.int64)
+        lmeta = np.zeros((max(B, 1), AUG_META), np.int64)
+        arrays = list(imgs) + lsegs + patches + [tables, params, meta, lmeta]
+        offs = self._upload_offsets(arrays)
+        pi = 0
+        for b, (img, d, g) in enumerate(zip(imgs, ds, geo)):
+            (x0, y0, cw, ch), (mode, xt, kx, yt, ky) = d['win'], g
+            row = [offs[b], img.shape[0], img.shape[1], img.shape[1] * 3, cw, ch, int(d['flip']), xt, yt, kx, ky, mode,
+                   0, 0, 0, 0, 0, 0, 0, 0]
+            if d['pm'] is not None:
+                row[12], row[13] = d['pm'][0], d['pm'][4]
+            if d['erase'] is not None:
+                ex, ey, ew, eh, patch = d['erase']
+                assert ex + ew <= cw and ey + eh <= ch
+                row[14:19] = [ex, ey, ew, eh, offs[nimg + len(lsegs) + pi]]
+                pi += 1
+            meta[b] = row
+        for b, (seg, d, (xt, kx, yt, ky)) in enumerate(zip(lsegs, ds, lgeo)):
+            x0, y0, cw, ch = d['win']
+            lmeta[b, :12] = [offs[nimg + b], seg.shape[0], seg.shape[1], seg.shape[1], cw, ch, int(d['flip']), xt, yt, kx,
+                             ky, RESAMPLE_NEAREST]
+        buf, offs = self._upload(arrays)
+        ptr = buf.data_ptr()
+        p_tab, p_prm, p_meta, p_lmeta = [ptr + o for o in offs[-4:]]
+        out = torch.empty((B, 3, Hout, Wout), dtype=torch.float32, device=self.device)
+        mean_keep, mean_p = _host_floats(self.mean)
+        std_keep, std_p = _host_floats(self.std)
+        lib.call('rscotr_img_aug_u8', ptr, p_meta, p_tab, p_prm, out.data_ptr(), B, Hout, Wout, mean_p, std_p,
+                 int(self.to_rgb), ops._stream())
+        metas = []
+        for im, d in zip(imgs, ds):
+            (sx, sy, sw, sh), (rw, rh), (x0, y0, cw, ch) = d['src'], d['rsz'], d['win']
+            m = dict(ori_shape=im.shape, img_shape=(ch, cw, 3), pad_shape=(Hout, Wout, 3), flip=d['flip'],
+                     flip_direction='horizontal' if d['flip'] else None, scale_factor=1.0,
+                     img_norm_cfg=dict(mean=self.mean, std=self.std, to_rgb=self.to_rgb))
+            if self.resize is not None or self.rrc is not None:
+                m['scale_factor'] = np.array([rw / sw, rh / sh, rw / sw, rh / sh], dtype=np.float32)
+                m['keep_ratio'] = bool(self.resize is not None and self.resize.get('keep_ratio') and 'size' not in self.resize)
+            metas.append(m)
+        batch = dict(img=out, img_metas=metas)
+        if self.task == 'cls':
+            batch['gt_label'] = torch.tensor([int(s['gt_label']) for s in samples], dtype=torch.int64, device=self.device)
+        elif self.task == 'det':
+            boxes, labels, hboxes, hlabels = [], [], [], []
+            for s, d, m in zip(samples, ds, metas):
+                hb = np.asarray(s['gt_bboxes'], dtype=np.float32).reshape(-1, 4)
+                if self.resize is not None or self.rrc is not None:
+                    hb = scale_boxes(hb, m['scale_factor'], m['img_shape'])
+                cw = d['win'][2]
+                if d['flip']:
+                    hb = np.stack([np.float32(cw) - hb[:, 2], hb[:, 1], np.float32(cw) - hb[:, 0], hb[:, 3]], -1)
+                hl = np.asarray(s['gt_labels'], dtype=np.int64).reshape(-1)
+                boxes.append(torch.from_numpy(np.ascontiguousarray(hb)).to(self.device))
+                labels.append(torch.from_numpy(np.ascontiguousarray(hl)).to(self.device))
+                hboxes.append(np.ascontiguousarray(hb))
+                hlabels.append(np.ascontiguousarray(hl))
+            batch['gt_bboxes'], batch['gt_labels'] = boxes, labels
+            batch['gt_bboxes_host'], batch['gt_labels_host'] = hboxes, hlabels
+        else:
+            lab = torch.empty((B, 1, Hout, Wout), dtype=torch.int64, device=self.device)
+            lib.call('rscotr_seg_label_aug_u8', ptr, p_lmeta, p_tab, lab.data_ptr(), B, Hout, Wout,
+                     int(self.reduce_zero_label), int(self.seg_pad_val), ops._stream())
+            batch['gt_semantic_seg'] = lab
+        return batch
+
+    @staticmethod
+    def _upload_offsets(arrays):
+        offs, o = [], 0
+        for a in arrays:
+            offs.append(o)
+            o = _round_up(o + a.nbytes, 16)
+        return offs
+
     def __call__(self, samples, rng=None):
         rng = rng or np.random
+        if self.augmented:
+            return self._call_augmented(samples, rng)
         B = len(samples)
         imgs = [s['img'] for s in samples]
         segs = [s.get('gt_semantic_seg') for s in samples]
@@ -151,6 +538,135 @@ def collate_for(task, device, **kw):
         return DeviceCollate('det', device, flip_prob=0.5, size_divisor=32, **kw)
     return DeviceCollate('seg', device, flip_prob=0.5, crop_size=(512, 512), cat_max_ratio=0.75, reduce_zero_label=True,
                          seg_pad_val=5, **kw)
+
+
+def scale_boxes(bboxes, scale_factor, img_shape):
+    """mmdet Resize._resize_bboxes with bbox_clip_border=True: float32 boxes * scale_factor, clipped to img_shape."""
+    b = np.asarray(bboxes, np.float32) * np.asarray(scale_factor, np.float32)
+    b[:, 0::2] = np.clip(b[:, 0::2], 0, img_shape[1])
+    b[:, 1::2] = np.clip(b[:, 1::2], 0, img_shape[0])
+    return b
+
+
+# the three dataset configs' augmentation settings (configs/_base_/cls/resisc_swin_224.py:10-35,43-48,
+# configs/_base_/det/dior.py:13-18,24-33, configs/_base_/seg/potsdam_IRRG_all.py:10-18,24-31); RandAugment is left out
+CLS_ERASING = dict(erase_prob=0.25, mode='rand', min_area_ratio=0.02, max_area_ratio=1 / 3,
+                   fill_color=IMG_NORM['mean'][::-1], fill_std=IMG_NORM['std'][::-1])
+
+
+def train_collate_for(task, device, **kw):
+    """The training pipelines' collate with the resampling and colour stages on the device:
+    cls RandomResizedCrop(224, bicubic, pillow) + RandomFlip + RandomErasing; det keep-ratio Resize((1333, 800)) + RandomFlip
+    + Pad(32); seg Resize((512, 512), ratio_range=(0.5, 2.0)) + RandomCrop(512, cat_max_ratio=0.75) + RandomFlip +
+    PhotoMetricDistortion + Pad(512, seg_pad_val=5).  Keyword arguments override these settings."""
+    if task == 'cls':
+        cfg = dict(flip_prob=0.5, random_resized_crop=dict(size=224), resize_backend='pillow', random_erasing=CLS_ERASING)
+    elif task == 'det':
+        cfg = dict(flip_prob=0.5, size_divisor=32, resize=dict(img_scale=(1333, 800)))
+    else:
+        cfg = dict(flip_prob=0.5, crop_size=(512, 512), cat_max_ratio=0.75, reduce_zero_label=True, seg_pad_val=5,
+                   resize=dict(img_scale=(512, 512), ratio_range=(0.5, 2.0)), photometric=True)
+    return DeviceCollate(task, device, **dict(cfg, **kw))
+
+
+def eval_collate_for(task, device, **kw):
+    """The test pipelines' collate (no flip): cls Resize((224, 224), bicubic, pillow); det keep-ratio Resize((1333, 800)) +
+    Pad(32); seg keep-ratio Resize((512, 512)) (val_pipeline: no Pad; a batch is padded to its largest image)."""
+    if task == 'cls':
+        cfg = dict(flip_prob=0.0, resize=dict(size=(224, 224)), resize_backend='pillow')
+    elif task == 'det':
+        cfg = dict(flip_prob=0.0, size_divisor=32, resize=dict(img_scale=(1333, 800)))
+    else:
+        cfg = dict(flip_prob=0.0, resize=dict(img_scale=(512, 512)))
+    return DeviceCollate(task, device, **dict(cfg, **kw))
+
+
+_PASSIVE = {'LoadImageFromFile', 'ImageToTensor', 'ToTensor', 'DefaultFormatBundle', 'Collect', 'Normalize'}
+
+
+def build_collate(task, pipeline_cfg, device, unsupported='raise'):
+    """Map an mm* pipeline (a list of transform dicts, as in the dataset configs) to a DeviceCollate.
+
+    Understood: LoadImageFromFile, LoadAnnotations (reduce_zero_label), Resize (mmseg / mmdet img_scale + ratio_range +
+    keep_ratio; mmcls size + backend + interpolation), RandomResizedCrop, RandomCrop, RandomFlip, PhotoMetricDistortion,
+    RandomErasing, Normalize, Pad, ImageToTensor, ToTensor, DefaultFormatBundle, Collect and MultiScaleFlipAug (its single
+    scale and its transforms; flip=False).  Anything else (RandAugment among them) raises NotImplementedError naming it,
+    unless unsupported='skip': then it is left out and listed in `collate.skipped`, and the random stream no longer matches
+    the reference's (the skipped transform's draws are not made)."""
+    assert unsupported in ('raise', 'skip')
+    kw, skipped, norm = dict(flip_prob=0.0), [], None
+
+    def visit(t, scale=None):
+        nonlocal norm
+        t = dict(t)
+        typ = t.pop('type')
+        if typ in _PASSIVE:
+            if typ == 'Normalize':
+                norm = t
+        elif typ == 'LoadAnnotations':
+            kw['reduce_zero_label'] = bool(t.get('reduce_zero_label', False))
+        elif typ == 'MultiScaleFlipAug':
+            if t.get('flip', False):
+                raise NotImplementedError('MultiScaleFlipAug(flip=True)')
+            sc = t.get('img_scale')
+            if isinstance(sc, list):
+                if len(sc) != 1:
+                    raise NotImplementedError('MultiScaleFlipAug with several scales')
+                sc = sc[0]
+            for u in t.get('transforms', []):
+                visit(u, tuple(sc) if sc is not None else None)
+        elif typ == 'Resize':
+            if 'size' in t:  # mmcls
+                size = t['size']
+                kw['resize'] = dict(size=(size, size) if isinstance(size, int) else tuple(size))
+            else:
+                sc = t.get('img_scale', scale)
+                if sc is None:  # MultiScaleFlipAug(img_scale=None, img_ratios=[1.0]): the image's own size
+                    return
+                if isinstance(sc, list):
+                    if len(sc) != 1:
+                        raise NotImplementedError('Resize with several img_scale values')
+                    sc = sc[0]
+                kw['resize'] = dict(img_scale=tuple(sc), ratio_range=t.get('ratio_range'), keep_ratio=t.get('keep_ratio', True))
+            kw['resize_backend'] = _backend(t)
+        elif typ == 'RandomResizedCrop':
+            kw['random_resized_crop'] = {k: t[k] for k in ('size', 'scale', 'ratio', 'max_attempts') if k in t}
+            kw['resize_backend'] = _backend(t)
+        elif typ == 'RandomCrop':
+            cs = t['crop_size']
+            kw['crop_size'] = (cs, cs) if isinstance(cs, int) else tuple(cs)
+            kw['cat_max_ratio'] = t.get('cat_max_ratio', 1.0)
+            kw['ignore_index'] = t.get('ignore_index', 255)
+        elif typ == 'RandomFlip':
+            kw['flip_prob'] = t.get('flip_prob', t.get('flip_ratio', t.get('prob', 0.0))) or 0.0
+        elif typ == 'PhotoMetricDistortion':
+            kw['photometric'] = dict(PHOTOMETRIC, **t)
+        elif typ == 'RandomErasing':
+            kw['random_erasing'] = dict(t)
+        elif typ == 'Pad':
+            if t.get('size_divisor'):
+                kw['size_divisor'] = t['size_divisor']
+            if t.get('size') is not None and 'crop_size' not in kw:
+                raise NotImplementedError('Pad(size=...) without RandomCrop')
+            kw['seg_pad_val'] = t.get('seg_pad_val', 255)
+        elif unsupported == 'skip':
+            skipped.append(typ)
+        else:
+            raise NotImplementedError(f'{typ} is not implemented by the device collate (build_collate(..., '
+                                      f"unsupported='skip') leaves it out)")
+    for t in pipeline_cfg:
+        visit(t)
+    col = DeviceCollate(task, device, img_norm_cfg=norm, **kw)
+    col.skipped = skipped
+    return col
+
+
+def _backend(t):
+    backend, interp = t.get('backend', 'cv2'), t.get('interpolation', 'bilinear')
+    if (backend, interp) not in (('cv2', 'bilinear'), ('pillow', 'bicubic')):
+        raise NotImplementedError(f'{t.get("type", "resize")}: backend={backend!r}, interpolation={interp!r} '
+                                  "(cv2 bilinear and pillow bicubic are implemented)")
+    return backend
 
 
 # --------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,305 @@
+"""NumPy restatement (test infrastructure only) of the resampling and colour transforms of the reference's dataset configs,
+applied per sample in the reference's order with its random draws, for the device path of rscotr_amd/pipeline.py
+(`rscotr_img_aug_u8`).  Written apart from pipeline.py on purpose: its tables are not reused here, so a host-side table bug
+shows up as a mismatch.  Crop / flip / normalize / pad are oracle/pipeline.py's.
+
+mmcv 1.6.1 / mmseg 0.28 / mmdet 2.25.1 / mmcls (unpinned upstream) are not installed; what they do is restated below.
+
+Resampling (mmcv imresize / imrescale):
+  nearest   cv2 INTER_NEAREST: sx = min(floor(x * ifx), W - 1), ifx = 1 / (dst_w / src_w) in float64.
+  bilinear  cv2 INTER_LINEAR on uint8, scalar fixed-point form: fx = float32((x + 0.5) * ifx - 0.5), sx = floor(fx),
+            fx -= sx; sx < 0 or sx >= W - 1 -> one tap (sx clamped, fx = 0); weights saturate_cast<short>(c * 2048) of
+            c = 1 - fx, fx (float32, round half to even); out = (sum wy * sum wx * p + 2^21) >> 22.  Parity with cv2 is
+            unpinned: +-1 LSB expected (its SIMD / IPP / exact-2x paths), unmeasured (cv2 is not installed).
+  bicubic   backend='pillow': Pillow itself, Image.fromarray(a).resize((w, h), Image.BICUBIC).
+
+PhotoMetricDistortion (mmseg 0.28, numpy.random):
+    convert(img, alpha=1, beta=0) = clip(img.astype(float32) * alpha + beta, 0, 255).astype(uint8)
+    brightness: if randint(2): convert(beta=uniform(-32, 32));  mode = randint(2);  if mode == 1: contrast
+    saturation: if randint(2): hsv = bgr2hsv(img); hsv[..., 1] = convert(hsv[..., 1], alpha=uniform(0.5, 1.5)); hsv2bgr
+    hue:        if randint(2): hsv = bgr2hsv(img); hsv[..., 0] = (hsv[..., 0].astype(int) + randint(-18, 18)) % 180; hsv2bgr
+    if mode == 0: contrast;   contrast: if randint(2): convert(alpha=uniform(0.5, 1.5))
+  bgr2hsv / hsv2bgr are cv2.cvtColor's uint8 forms (RGB2HSV_b with hsv_shift = 12 and the sdiv / hdiv180 tables;
+  HSV2RGB_b: s * (1 / 255) in float32, HSV2RGB_native's sector form, saturate_cast rounding) -- restated from the OpenCV
+  source, not checked against cv2 (absent).
+
+RandomErasing (mmcls; restated):
+    def __call__(self, results):
+        if np.random.rand() > self.erase_prob: return results
+        img_h, img_w = img.shape[:2]
+        log_aspect_range = np.log(np.array(self.aspect_range, dtype=np.float32))
+        aspect_ratio = np.exp(np.random.uniform(*log_aspect_range))
+        area = img_h * img_w
+        area *= np.random.uniform(self.min_area_ratio, self.max_area_ratio)
+        h = min(int(round(np.sqrt(area * aspect_ratio))), img_h)
+        w = min(int(round(np.sqrt(area / aspect_ratio))), img_w)
+        top = np.random.randint(0, img_h - h) if img_h > h else 0
+        left = np.random.randint(0, img_w - w) if img_w > w else 0
+        img = self._fill_pixels(img, top, left, h, w)
+    def _fill_pixels(self, img, top, left, h, w):
+        if self.mode == 'const': patch = np.empty((h, w, 3), np.uint8); patch[:, :] = np.array(self.fill_color, np.uint8)
+        elif self.fill_std is None: patch = np.random.uniform(0, 256, (h, w, 3)).astype(np.uint8)
+        else: patch = np.clip(np.random.normal(self.fill_color, self.fill_std, (h, w, 3)).astype(np.int32), 0, 255).astype(np.uint8)
+        img[top:top + h, left:left + w] = patch
+
+RandomResizedCrop.get_params (mmcls, numpy.random): 10 attempts of target_area = uniform(*scale) * area, aspect =
+exp(uniform(log r0, log r1)), w = int(round(sqrt(area * aspect))), h = int(round(sqrt(area / aspect))); accepted when
+0 < w <= W and 0 < h <= H with offsets randint(0, H - h + 1), randint(0, W - w + 1); else the central crop.
+
+Resize (mmseg / mmdet, keep_ratio): ratio = random_sample() * (hi - lo) + lo; scale = int(s0 * ratio), int(s1 * ratio);
+mmcv rescale_size: sf = min(max(scale) / max(h, w), min(scale) / min(h, w)), new = int(w * sf + 0.5), int(h * sf + 0.5);
+scale_factor = float32 [new_w / w, new_h / h] * 2.  Boxes (mmdet, bbox_clip_border=True): float32 boxes * scale_factor,
+x clipped to [0, img_w], y to [0, img_h]."""
+import math
+
+import numpy as np
+from PIL import Image
+
+from oracle import pipeline as OP
+
+
+# ---- resampling ---------------------------------------------------------------------------------------------------------
+def resize_nearest(a, w, h):
+    H, W = a.shape[:2]
+    ys = np.minimum(np.floor(np.arange(h) * (1.0 / (h / H))).astype(np.int64), H - 1)
+    xs = np.minimum(np.floor(np.arange(w) * (1.0 / (w / W))).astype(np.int64), W - 1)
+    return a[ys][:, xs]
+
+
+def _linear_axis(n_in, n_out):
+    lo, hi, w_lo, w_hi = [], [], [], []
+    ifx = 1.0 / (n_out / n_in)
+    for o in range(n_out):
+        fx = np.float32((o + 0.5) * ifx - 0.5)
+        sx = int(math.floor(fx))
+        fx = np.float32(fx - np.float32(sx))
+        if sx < 0:
+            sx, fx = 0, np.float32(0)
+        if sx >= n_in - 1:
+            sx, fx = n_in - 1, np.float32(0)
+        lo.append(sx)
+        hi.append(min(sx + 1, n_in - 1))
+        w_lo.append(int(np.rint(np.float32(np.float32(1) - fx) * np.float32(2048))))
+        w_hi.append(int(np.rint(fx * np.float32(2048))))
+    return np.array(lo), np.array(hi), np.array(w_lo, np.int64), np.array(w_hi, np.int64)
+
+
+def resize_bilinear(a, w, h):
+    """uint8 HWC -> uint8 (h, w, C), the fixed-point rule above."""
+    H, W = a.shape[:2]
+    x0, x1, wx0, wx1 = _linear_axis(W, w)
+    y0, y1, wy0, wy1 = _linear_axis(H, h)
+    p = a.astype(np.int64)
+    r0 = p[y0][:, x0] * wx0[None, :, None] + p[y0][:, x1] * wx1[None, :, None]
+    r1 = p[y1][:, x0] * wx0[None, :, None] + p[y1][:, x1] * wx1[None, :, None]
+    v = (r0 * wy0[:, None, None] + r1 * wy1[:, None, None] + (1 << 21)) >> 22
+    return np.clip(v, 0, 255).astype(np.uint8)
+
+
+def resize_bicubic_pil(a, w, h):
+    return np.asarray(Image.fromarray(np.ascontiguousarray(a)).resize((w, h), Image.BICUBIC))
+
+
+def resize_img(a, w, h, backend):
+    if (w, h) == (a.shape[1], a.shape[0]):
+        return a
+    return resize_bicubic_pil(a, w, h) if backend == 'pillow' else resize_bilinear(a, w, h)
+
+
+# ---- photometric ----------------------------------------------------------------------------------------------------
+def convert(img, alpha=1, beta=0):
+    img = img.astype(np.float32) * np.float32(alpha) + np.float32(beta)
+    return np.clip(img, 0, 255).astype(np.uint8)
+
+
+def _cv_round(x):
+    return np.rint(x).astype(np.int64)
+
+
+SDIV = np.array([0] + [int(_cv_round((255 << 12) / (1.0 * i))) for i in range(1, 256)], np.int64)
+HDIV180 = np.array([0] + [int(_cv_round((180 << 12) / (6.0 * i))) for i in range(1, 256)], np.int64)
+
+
+def bgr2hsv(img):
+    p = img.astype(np.int64)
+    b, g, r = p[..., 0], p[..., 1], p[..., 2]
+    v = np.maximum(np.maximum(b, g), r)
+    vmin = np.minimum(np.minimum(b, g), r)
+    diff = v - vmin
+    s = (diff * SDIV[v] + (1 << 11)) >> 12
+    h = np.where(v == r, g - b, np.where(v == g, b - r + 2 * diff, r - g + 4 * diff))
+    h = (h * HDIV180[diff] + (1 << 11)) >> 12
+    h = np.where(h < 0, h + 180, h)
+    return np.stack([h, s, v], -1).astype(np.uint8)
+
+
+def hsv2bgr(hsv):
+    f32 = np.float32
+    h = hsv[..., 0].astype(f32) * (f32(6.0) / f32(180))
+    s = hsv[..., 1].astype(f32) * (f32(1.0) / f32(255.0))
+    v = hsv[..., 2].astype(f32)
+    h = np.fmod(h, f32(6.0))
+    sector = np.floor(h).astype(np.int64)
+    h = (h - sector.astype(f32)).astype(f32)
+    bad = (sector < 0) | (sector >= 6)
+    sector = np.where(bad, 0, sector)
+    h = np.where(bad, f32(0), h).astype(f32)
+    tab = np.stack([v, v * (f32(1) - s), v * (f32(1) - s * h), v * (f32(1) - s * (f32(1) - h))], -1).astype(f32)
+    sd = np.array([[1, 3, 0], [1, 0, 2], [3, 0, 1], [0, 2, 1], [0, 1, 3], [2, 1, 0]])[sector]
+    bgr = np.take_along_axis(tab, sd, -1)
+    grey = (s == 0)[..., None]
+    bgr = np.where(grey, v[..., None], bgr)
+    return np.clip(np.rint(bgr), 0, 255).astype(np.uint8)
+
+
+def photometric(img, rng, brightness_delta=32, contrast_range=(0.5, 1.5), saturation_range=(0.5, 1.5), hue_delta=18):
+    def contrast(img):
+        if rng.randint(2):
+            return convert(img, alpha=rng.uniform(*contrast_range))
+        return img
+    if rng.randint(2):
+        img = convert(img, beta=rng.uniform(-brightness_delta, brightness_delta))
+    mode = rng.randint(2)
+    if mode == 1:
+        img = contrast(img)
+    if rng.randint(2):
+        hsv = bgr2hsv(img)
+        hsv[..., 1] = convert(hsv[..., 1], alpha=rng.uniform(*saturation_range))
+        img = hsv2bgr(hsv)
+    if rng.randint(2):
+        hsv = bgr2hsv(img)
+        hsv[..., 0] = (hsv[..., 0].astype(int) + rng.randint(-hue_delta, hue_delta)) % 180
+        img = hsv2bgr(hsv)
+    if mode == 0:
+        img = contrast(img)
+    return img
+
+
+# ---- erasing, random resized crop, rescale, boxes ----------------------------------------------------------------------
+def random_erasing(img, rng, erase_prob=0.5, min_area_ratio=0.02, max_area_ratio=0.4, aspect_range=(3 / 10, 10 / 3),
+                   mode='const', fill_color=(128, 128, 128), fill_std=None):
+    if rng.rand() > erase_prob:
+        return img
+    img = img.copy()
+    img_h, img_w = img.shape[:2]
+    log_aspect_range = np.log(np.array(aspect_range, dtype=np.float32))
+    aspect_ratio = np.exp(rng.uniform(*log_aspect_range))
+    area = img_h * img_w
+    area *= rng.uniform(min_area_ratio, max_area_ratio)
+    h = min(int(round(np.sqrt(area * aspect_ratio))), img_h)
+    w = min(int(round(np.sqrt(area / aspect_ratio))), img_w)
+    top = rng.randint(0, img_h - h) if img_h > h else 0
+    left = rng.randint(0, img_w - w) if img_w > w else 0
+    if mode == 'const':
+        patch = np.empty((h, w, 3), dtype=np.uint8)
+        patch[:, :] = np.array(fill_color, dtype=np.uint8)
+    elif fill_std is None:
+        patch = rng.uniform(0, 256, (h, w, 3)).astype(np.uint8)
+    else:
+        patch = np.clip(rng.normal(fill_color, fill_std, (h, w, 3)).astype(np.int32), 0, 255).astype(np.uint8)
+    img[top:top + h, left:left + w] = patch
+    return img
+
+
+def rrc_params(H, W, rng, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.), max_attempts=10):
+    area = H * W
+    for _ in range(max_attempts):
+        target_area = rng.uniform(*scale) * area
+        aspect = math.exp(rng.uniform(math.log(ratio[0]), math.log(ratio[1])))
+        tw = int(round(math.sqrt(target_area * aspect)))
+        th = int(round(math.sqrt(target_area / aspect)))
+        if 0 < tw <= W and 0 < th <= H:
+            return rng.randint(0, H - th + 1), rng.randint(0, W - tw + 1), th, tw
+    r = W / H
+    if r < min(ratio):
+        tw, th = W, int(round(W / min(ratio)))
+    elif r > max(ratio):
+        th, tw = H, int(round(H * max(ratio)))
+    else:
+        tw, th = W, H
+    return (H - th) // 2, (W - tw) // 2, th, tw
+
+
+def rescale_wh(w, h, scale):
+    sf = min(max(scale) / max(h, w), min(scale) / min(h, w))
+    return int(w * float(sf) + 0.5), int(h * float(sf) + 0.5)
+
+
+def scale_factor(w, h, nw, nh):
+    return np.array([nw / w, nh / h, nw / w, nh / h], dtype=np.float32)
+
+
+def boxes_rescale(b, sf, img_shape):
+    b = b.astype(np.float32) * sf
+    b[:, 0::2] = np.clip(b[:, 0::2], 0, img_shape[1])
+    b[:, 1::2] = np.clip(b[:, 1::2], 0, img_shape[0])
+    return b
+
+
+# ---- the three training pipelines, per sample, and their collate ---------------------------------------------------------
+def _crop_seg(H, W, lab, rng, crop, cat_max_ratio, reduce_zero):
+    ch, cw = crop
+
+    def draw():
+        oy, ox = rng.randint(0, max(H - ch, 0) + 1), rng.randint(0, max(W - cw, 0) + 1)
+        return ox, oy, min(cw, W - ox), min(ch, H - oy)
+    win = draw()
+    if cat_max_ratio < 1.0:
+        for _ in range(10):
+            x0, y0, w, h = win
+            l, cnt = np.unique(lab[y0:y0 + h, x0:x0 + w], return_counts=True)
+            cnt = cnt[(l != 0) & (l != 255)] if reduce_zero else cnt[l != 255]
+            if len(cnt) > 1 and cnt.max() / cnt.sum() < cat_max_ratio:
+                break
+            win = draw()
+    return win
+
+
+def seg_sample(img, lab, rng, img_scale=(512, 512), ratio_range=(0.5, 2.0), crop=(512, 512), cat_max_ratio=0.75,
+               flip_prob=0.5, photo=True, reduce_zero=True):
+    """mmseg Resize -> RandomCrop -> RandomFlip -> PhotoMetricDistortion -> uint8 image, raw label window, metas."""
+    H, W = img.shape[:2]
+    ratio = rng.random_sample() * (ratio_range[1] - ratio_range[0]) + ratio_range[0]
+    nw, nh = rescale_wh(W, H, (int(img_scale[0] * ratio), int(img_scale[1] * ratio)))
+    im = resize_img(img, nw, nh, 'cv2')
+    lb = resize_nearest(lab, nw, nh)
+    x0, y0, w, h = _crop_seg(nh, nw, lb, rng, crop, cat_max_ratio, reduce_zero)
+    im, lb = im[y0:y0 + h, x0:x0 + w], lb[y0:y0 + h, x0:x0 + w]
+    fl = bool(rng.rand() < flip_prob)
+    if fl:
+        im, lb = OP.imflip(im), OP.imflip(lb)
+    if photo:
+        im = photometric(im, rng)
+    return im, lb, dict(flip=fl, img_shape=(h, w, 3), scale_factor=scale_factor(W, H, nw, nh))
+
+
+def cls_sample(img, rng, size=224, flip_prob=0.5, erasing=None, backend='pillow'):
+    """mmcls RandomResizedCrop -> RandomFlip -> RandomErasing."""
+    H, W = img.shape[:2]
+    oy, ox, th, tw = rrc_params(H, W, rng)
+    im = resize_img(img[oy:oy + th, ox:ox + tw], size, size, backend)
+    fl = bool(rng.rand() < flip_prob)
+    if fl:
+        im = OP.imflip(im)
+    if erasing is not None:
+        im = random_erasing(im, rng, **erasing)
+    return im, dict(flip=fl, crop=(ox, oy, tw, th), scale_factor=scale_factor(tw, th, size, size))
+
+
+def det_sample(img, boxes, rng, img_scale=(1333, 800), flip_prob=0.5):
+    """mmdet Resize(keep_ratio) -> RandomFlip; boxes scaled, clipped, flipped."""
+    H, W = img.shape[:2]
+    nw, nh = rescale_wh(W, H, img_scale)
+    im = resize_img(img, nw, nh, 'cv2')
+    sf = scale_factor(W, H, nw, nh)
+    b = boxes_rescale(np.asarray(boxes, np.float32).reshape(-1, 4), sf, (nh, nw))
+    fl = bool(rng.rand() < flip_prob)
+    if fl:
+        im = OP.imflip(im)
+        b = OP.bbox_flip(b, np.float32(nw))
+    return im, b, dict(flip=fl, img_shape=(nh, nw, 3), scale_factor=sf)
+
+
+def collate_images(ims, out_hw, mean, std, to_rgb=True):
+    return np.stack([np.ascontiguousarray(OP.impad(OP.imnormalize(im, mean, std, to_rgb), out_hw, 0).transpose(2, 0, 1))
+                     for im in ims])
