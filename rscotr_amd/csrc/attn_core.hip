@@ -34,15 +34,7 @@
 // register prefetch of the next tile's operands, per kernel.  OFF: a set costs 36 / 52 / 70 registers, the passes then fit one
 // wavefront per SIMD instead of two, and two resident workgroups hide each other's load latency better than the prefetch does
 // (in the step: 35.19 ms per round without any, 35.35 with all three; profiles/r4_attn_core.txt)
-#ifndef ATTN_PF_FWD
-#define ATTN_PF_FWD 0
-#endif
-#ifndef ATTN_PF_DQ
-#define ATTN_PF_DQ 0
-#endif
-#ifndef ATTN_PF_DKV
-#define ATTN_PF_DKV 0
-#endif
+constexpr bool ATTN_PF_FWD = false, ATTN_PF_DQ = false, ATTN_PF_DKV = false;
 
 namespace rscotr {
 
@@ -568,9 +560,7 @@ int check_attn(const char* what, const void* const* ptrs, int nptr, int B, int h
 
 using namespace rscotr;
 
-#ifndef ATTN_NW
-#define ATTN_NW 4  // wavefronts per workgroup: they split the walk over the key (query) tiles (8: 35.2 ms per round, 4: 35.0)
-#endif
+constexpr int ATTN_NW = 4;  // wavefronts per workgroup: they split the walk over the key (query) tiles (8: 35.2 ms per round, 4: 35.0)
 static_assert(ATTN_NW >= 4, "the combine stages use 256 threads");
 
 extern "C" int64_t rscotr_attn_core_workspace(int B, int heads, int Lq, int Lk) {

@@ -121,11 +121,7 @@ __device__ __forceinline__ void amax_commit(unsigned* slot, float amx) {
   for (int o = 32; o > 0; o >>= 1) amx = fmaxf(amx, __shfl_xor(amx, o, 64));
   if ((threadIdx.x & 63) == 0) {
     const unsigned b = __float_as_uint(amx) & 0x7fffffffu;
-#ifdef RSCOTR_RANGE_UNDER  // (experiment, profiles/r6_range_words.txt: words RSCOTR_RANGE_UNDER binades too small — what a lost maximum does to a step)
-    if (b) range_mark(slot, max(range_byte(b) - RSCOTR_RANGE_UNDER, 0));
-#else
     if (b) range_mark(slot, range_byte(b));
-#endif
   }
 }
 

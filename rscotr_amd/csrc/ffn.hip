@@ -44,9 +44,7 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 constexpr int FFN_HC = 128;    // hidden columns per chunk (4 A wavefronts x 32)
 constexpr int FFN_LDRB = 160;  // bytes per LDS row of a 32-k stage: h[32] | l[32] | 32 bytes pad (conflict-free ds_read_b128 of the
                                // 16 x 16 x 32 fragment pattern: row = lane & 15, 16 bytes at k = 8 (lane >> 4))
-#ifndef FFN_DB
-#define FFN_DB 1  // k steps (of 32) the B role's weight fragment loads run ahead of their MFMAs
-#endif
+constexpr int FFN_DB = 1;  // k steps (of 32) the B role's weight fragment loads run ahead of their MFMAs
 
 // MODE: what happens to a hidden chunk between the two products
 enum { FFN_RELU = 0,       // hidden = relu(x W1^T + b1); one bit per element [hidden > 0] -> bits
@@ -101,16 +99,12 @@ __device__ __forceinline__ void store_b128(float4 v, __amdgpu_buffer_rsrc_t r, i
   __builtin_amdgcn_sched_barrier(0);
 }
 
-#ifndef FFN_STAG_MINC
-#define FFN_STAG_MINC 192  // narrowest width whose launches rotate their chunk order: 8192 x 192 -> 768 cold 45.6 / 41.5 -> 38.2 / 37.6 us with it; C = 96 (held to
-                           // 128 registers, where the rotation's index arithmetic spills) 57 -> 61: stays in order
-#endif
-#ifndef FFN_PHASES
-#define FFN_PHASES 4  // distinct starting chunks among the workgroups that share an L2.  16 (every chunk of 256 -> 2048 a starting point) spreads the
-                      // cold requests widest but puts all 4 MB of both weights' planes into the working set of a 4 MB L2 next to the 89 MB hidden
-                      // stream: 2 x 155 MiB fetched per launch against 2 x 27 without rotation (scripts/lab/pmc_ffn_traffic.sh); 4: 2 x 77 MiB, the
-                      // same launch time cold and in the step (29.66-29.72 ms per round; 8: 29.64-29.65; 16: 29.72-29.79; 2: 29.96-29.99)
-#endif
+constexpr int FFN_STAG_MINC = 192;  // narrowest width whose launches rotate their chunk order: 8192 x 192 -> 768 cold 45.6 / 41.5 -> 38.2 / 37.6 us with it; C = 96 (held to
+                                    // 128 registers, where the rotation's index arithmetic spills) 57 -> 61: stays in order
+constexpr int FFN_PHASES = 4;  // distinct starting chunks among the workgroups that share an L2.  16 (every chunk of 256 -> 2048 a starting point) spreads the
+                               // cold requests widest but puts all 4 MB of both weights' planes into the working set of a 4 MB L2 next to the 89 MB hidden
+                               // stream: 2 x 155 MiB fetched per launch against 2 x 27 without rotation (scripts/lab/pmc_ffn_traffic.sh); 4: 2 x 77 MiB, the
+                               // same launch time cold and in the step (29.66-29.72 ms per round; 8: 29.64-29.65; 16: 29.72-29.79; 2: 29.96-29.99)
 // first chunk of workgroup j (of those sharing the weights through one L2) in a run of n chunks
 __device__ __forceinline__ int ffn_phase(int j, int n) {
   const int ph = n < FFN_PHASES ? n : FFN_PHASES;
@@ -123,11 +117,9 @@ __device__ __forceinline__ f32x4_t mfma16(uint4 a, uint4 b, f32x4_t c) {
 
 // Bit layout of FFN_RELU / FFN_RELU_GATE (opaque to callers, the same in both directions): uint32 [row tile][chunk][A wavefront][lane],
 // bit (it * NT + n) * 4 + r = accumulator register r of the lane's 16 x 16 tile (column tile it, row tile n).
+constexpr int FFN_SWIN_WAVES = 4;  // wavefronts per SIMD the C = 96 kernels are held to (4 = 128 registers: two 8-wavefront workgroups per CU; stage 1 of
+                                   // Swin-T at 512^2 is 1024 workgroups; C = 192 is 256 workgroups = one per CU, C = 256 needs its 123 KB of LDS alone)
 template <int C, int NT, int MODE, bool LN = false>
-#ifndef FFN_SWIN_WAVES
-#define FFN_SWIN_WAVES 4  // wavefronts per SIMD the C = 96 kernels are held to (4 = 128 registers: two 8-wavefront workgroups per CU; stage 1 of
-                          // Swin-T at 512^2 is 1024 workgroups; C = 192 is 256 workgroups = one per CU, C = 256 needs its 123 KB of LDS alone)
-#endif
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 96 ? FFN_SWIN_WAVES : 2, C == 96 ? FFN_SWIN_WAVES : 2))) void ffn_h3_kernel(FfnParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ffn_lds[];
   constexpr bool GATE = MODE == FFN_RELU_GATE, GELU = MODE == FFN_GELU, GGRAD = MODE == FFN_GELU_GRAD;
@@ -177,11 +169,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 96 ? F
   auto ld_b = [&](int t, int it, int pl) {  // t: global k-step index c * 4 + ks = the k step of W2op
     return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rW, vW, it * nks2 * 2048 + t * 2048 + pl * 1024, 0));
   };
-#ifdef FFN_NO_STAGGER
-  const int c0r = cbase;
-#else
   const int c0r = cbase + (C >= FFN_STAG_MINC ? ffn_phase(jx, nloc) : 0);  // (= chunk_of(0) below: the first chunk of this workgroup)
-#endif
   uint4 ring[RING];
   if (role_a) {
 #pragma unroll
@@ -307,11 +295,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 96 ? F
   // cold for that L2 in the step, where twelve layers' plane sets pass through it per iteration — and then all hit the same lines.
   // Loop index c -> chunk (c + c0) % nch; the image parity stays the loop index's.  (The order of the output's partial sums
   // becomes a function of the row tile: still fixed by the launch geometry, bit-reproducible.)
-#ifdef FFN_NO_STAGGER
-  const int c0 = 0;
-#else
   const int c0 = C >= FFN_STAG_MINC ? ffn_phase(jx, nloc) : 0;  // (C = 96 stays in order: FFN_STAG_MINC)
-#endif
   auto chunk_of = [&](int c) {
     if constexpr (C < FFN_STAG_MINC) return cbase + c;
     const int v = c + c0;
@@ -366,16 +350,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 96 ? F
       unsigned ab[3], cd[3];
       split_pair_h(v[0], v[1], hh, ab);
       split_pair_h(v[2], v[3], hh, cd);
-#ifndef FFN_ABL_NOIMG
       unsigned char* dst = hs + (cl & 1) * (HST * STG) + wr * STG + li * FFN_LDRB + kg * 8 + n * 16 * FFN_LDRB + it * 32;
       *reinterpret_cast<uint2*>(dst) = make_uint2(ab[0], cd[0]);
       *reinterpret_cast<uint2*>(dst + 64) = make_uint2(ab[1], cd[1]);
-#else
-      asm volatile("" ::"v"(ab[0]), "v"(ab[1]), "v"(cd[0]), "v"(cd[1]));
-#endif
-#ifndef FFN_ABL_NOHID  // (FFN_ABL_*: timing ablations of scripts/lab/ffn_abl.sh — results are wrong with any of them)
       store_b128(make_float4(v[0], v[1], v[2], v[3]), rH, vH, soff);
-#endif
     };
     auto pre_epi = [&](int cl) {  // what the tiles of chunk cl need from memory: requested a k loop ahead of their first use
       const int cp = chunk_of(cl);
@@ -422,10 +400,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 96 ? F
           for (int n = 0; n < NT; ++n) hb[it][n] = mfma16(wl, xh[n], hb[it][n]);
 #pragma unroll
           for (int n = 0; n < NT; ++n) ha[it][n] = mfma16(wh, xh[n], ha[it][n]);
-#ifndef FFN_ABL_NOB
           if (ks + DA < KS1) { ring[slot] = ld_a(cw, ks + DA, it, 0); ring[slot + 1] = ld_a(cw, ks + DA, it, 1); }
           else { ring[slot] = ld_a(cn, ks + DA - KS1, it, 0); ring[slot + 1] = ld_a(cn, ks + DA - KS1, it, 1); }
-#endif
         }
         if constexpr (EPI) {
 #pragma unroll
@@ -446,18 +422,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 96 ? F
           pv[it][n].w = fmaf(hb[it][n][3], 0x1p-11f, ha[it][n][3]) * invx * inv1;
         }
     };
-#ifdef FFN_ABL_NOPIPE  // (timing ablation: every chunk's epilogue right behind its own k loop; the B role then reads an image too early)
-#pragma unroll 1
-    for (int c = 0; c < nloc; ++c) {
-      kloop(c, std::false_type{});
-#pragma unroll
-      for (int t = 0; t < 2 * NT; ++t) slice(c, t / NT, t % NT);
-      if constexpr (MODE == FFN_RELU) p.bits[(((long)bx * nch + chunk_of(c)) * 4 + wr) * 64 + lane] = bits;
-      __syncthreads();
-    }
-    __syncthreads();
-    __syncthreads();
-#else
     kloop(0, std::false_type{});
     __syncthreads();
 #pragma unroll 1
@@ -470,7 +434,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 96 ? F
     if constexpr (MODE == FFN_RELU) p.bits[(((long)bx * nch + chunk_of(nloc - 1)) * 4 + wr) * 64 + lane] = bits;
     __syncthreads();  // the last image is complete
     __syncthreads();  // (the B role's last barrier)
-#endif
     amax_commit(p.amax_hid, __uint_as_float(amxu));
   } else {
     f32x4_t ya[TPB][NT], yb[TPB][NT];  // y tiles: columns (wr * TPB + it) * 16 .., rows n * 16 ..
@@ -486,7 +449,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 96 ? F
       // ---- y += chunk c W2[:, chunk]^T: 4 k steps of 32
       const unsigned char* img = hs + (c & 1) * (HST * STG) + fo;
       const int cb = chunk_of(c);
-#ifndef FFN_ABL_NOPHASEB
       if (active) {
 #pragma unroll 1
         for (int kq = 0; kq < HST / FFN_DB; ++kq)
@@ -514,14 +476,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 96 ? F
               for (int n = 0; n < NT; ++n) yb[it][n] = mfma16(wl, gh[n], yb[it][n]);
 #pragma unroll
               for (int n = 0; n < NT; ++n) ya[it][n] = mfma16(wh, gh[n], ya[it][n]);
-#ifndef FFN_ABL_NOB
               ring[slot] = ld_b(tn, it, 0);  // (after the slot's last use: see the A role)
               ring[slot + 1] = ld_b(tn, it, 1);
-#endif
             }
           }
       }
-#endif
       __syncthreads();  // image c % 2 has been consumed
     }
     // ---- y = ((h h + (l h + h l) 2^-11) 2^-(s_hidden + s_w2) + b2) * yscale (+ resid): four consecutive columns of a row per lane
@@ -845,10 +804,8 @@ static int ffn_rows(int M, int C) {
 // applies bias / scale / residual / range word.  splits = the smallest divisor of the chunk count that brings the launch to 200
 // workgroups, runs of at least two chunks (the roles' pipeline); 1 for every launch that fills the chip by its rows.
 extern "C" int rscotr_ffn_h3_splits(int M, int C, int H) {
-  static const int forced = getenv("RSCOTR_FFN_SPLITS") ? atoi(getenv("RSCOTR_FFN_SPLITS")) : 0;  // (A/B runs: 1 = never)
   if (H < FFN_HC || H % FFN_HC) return 1;
   const int bm = ffn_rows(M, C), tiles = (M + bm - 1) / bm, nch = H / FFN_HC;
-  if (forced > 0) return nch % forced == 0 ? forced : 1;
   if (tiles >= 200) return 1;
   for (int d = 2; d <= nch / 2; ++d)
     if (nch % d == 0 && tiles * d >= 200) return d;
@@ -931,8 +888,7 @@ static int ffn_h3_run(const float* X, int M, int C, int H, const void* W1f, cons
   p.splits = splits; p.slabs = workspace;
   p.ln_g = ln.g; p.ln_b = ln.b; p.ln_eps = ln.eps; p.ln_out = ln.out; p.ln_mean = ln.mean; p.ln_rstd = ln.rstd;
   p.amax_g = ln.amax_g; p.amax_bt = ln.amax_b; p.amax_ln = ln.amax_out;
-  static const int xcd_ok = getenv("RSCOTR_FFN_SPLIT_XCD") ? atoi(getenv("RSCOTR_FFN_SPLIT_XCD")) : 1;  // (A/B runs)
-  if (splits > 1 && 8 % splits == 0 && xcd_ok) {
+  if (splits > 1 && 8 % splits == 0) {
     const int bm0 = ffn_rows(M, C), tiles = (M + bm0 - 1) / bm0, per = 8 / splits;  // XCDs per run
     p.by_xcd = 1; p.tpx = (tiles + per - 1) / per;
   }
@@ -1026,10 +982,7 @@ static int lin_h3_run(const float* X, int M, int N, int K, const void* Wf, const
   if (K == 1152 && M >= 8192) return fail(RSCOTR_E_SHAPE, "lin_h3: K = 1152 is a few-row width (M=%d)", M);
   hipStream_t s = static_cast<hipStream_t>(stream);
   ProfScope prof(PROF_GEMM, 2.0 * M * (double)N * K, s, "rscotr::lin_h3_kernel<%d, %s>", K, ln.g ? "true" : "false");
-  static const int rows64 = getenv("RSCOTR_LIN_ROWS64") ? atoi(getenv("RSCOTR_LIN_ROWS64")) : 0;  // (A/B: 64-row workgroups at K = 96)
-  if (rows64 && K == 96 && M >= 16384) {
-    if (ln.g) lin_launch<96, true, 4>(p, s); else lin_launch<96, false, 4>(p, s);
-  } else if (ln.g) {
+  if (ln.g) {
     if (K == 96) lin_launch<96, true>(p, s);
     else if (K == 192) lin_launch<192, true>(p, s);
     else lin_launch<384, true>(p, s);
@@ -1041,11 +994,7 @@ static int lin_h3_run(const float* X, int M, int N, int K, const void* Wf, const
     case 288: lin_launch<288, false>(p, s); break;
     case 384: lin_launch<384, false>(p, s); break;
     case 576: lin_launch<576, false>(p, s); break;
-    case 768: {
-      static const int rows16 = getenv("RSCOTR_LIN_ROWS16") ? atoi(getenv("RSCOTR_LIN_ROWS16")) : 0;  // (A/B: 16-row workgroups for the 512-row launches of Swin stage 4)
-      if (rows16 && M <= 1024) lin_launch<768, false, 1>(p, s); else lin_launch<768, false>(p, s);
-      break;
-    }
+    case 768: lin_launch<768, false>(p, s); break;
     default: lin_launch<1152, false, 1>(p, s); break;  // (16-row workgroups: 92 KB of planes)
   }
   return check_launch("lin_h3");

@@ -37,11 +37,9 @@
 #include <set>
 #include <type_traits>
 
-#ifndef RSCOTR_GEMM_PREC_DEFAULT
-#define RSCOTR_GEMM_PREC_DEFAULT 3
-#endif
-
 namespace rscotr {
+
+constexpr int GEMM_PREC_DEFAULT = 3;
 
 // Load the (R rows x 16 k) operand tile at (row0, k0) into registers: NV float4 per thread.
 template <int R, bool KMAJOR>
@@ -353,12 +351,8 @@ __device__ __forceinline__ void gemm_f32_body(GemmParams& p, const int bx, const
   const bool one_extra = MT == 1 && NT == 1 && !p.C2 &&
                          ((p.act == ACT_RELU_GRAD || p.act == ACT_GELU_GRAD) ? 1 : 0) + (p.resid ? 1 : 0) + (p.accumulate ? 1 : 0) == 1;
   // an activation (and / or the stored pre-activation) but no tensor to read: epilogue_noload16
-#ifdef RSCOTR_NO_NOLOAD  // (A/B builds: scripts/build_variant.sh)
-  const bool noload = false;
-#else
   const bool noload = !plain && (p.act == ACT_NONE || p.act == ACT_RELU || p.act == ACT_GELU) && !p.resid && !p.accumulate &&
                       !p.rowscale && !p.C2;
-#endif
   float amx = 0.f;
 #pragma unroll
   for (int i = 0; i < MT; ++i)
@@ -644,26 +638,17 @@ struct PlaneOperandH {
 };
 
 // PIPE: 0 = one LDS stage, two barriers per k-tile of 16; 1 = two LDS stages, one barrier, next tile's loads one step ahead;
-// 2 / 3 = the software-pipelined loop (two LDS stages, one barrier): the loads of tile t + D are issued at the top of step t
-// into the register set step t - 1 freed (D = 2 / 3 sets), and the split / pack / LDS writes of tile t + 1 are interleaved
+// 2 = the software-pipelined loop (two LDS stages, one barrier): the loads of tile t + D are issued at the top of step t
+// into the register set step t - 1 freed (D = 2 sets), and the split / pack / LDS writes of tile t + 1 are interleaved
 // with the MFMAs of tile t inside the wavefront (sched_group_barrier: 1 MFMA : 4 VALU : 1 DS write) — the conversion runs in
 // the shadow of the matrix pipe instead of in a phase of its own.  PIPE 2 stages 32 k per step (64 x 64 tiles: a row-major
-// operand row is one whole 128-byte line per step; half as many barriers), PIPE 3 stages 16 (128 x 128 tiles: LDS).
+// operand row is one whole 128-byte line per step; half as many barriers).  (A 128 x 128 form of the pipelined loop, 16 k
+// per step, measured slower on every layout of the step: +0.65 ms per round.)
 __device__ const float bf16x6_one = 1.f;
-#ifndef RSCOTR_X6_BK0
-#define RSCOTR_X6_BK0 32  // k per barrier pair of the one-stage loop (PIPE 0: the 128 x 128 kernels, the grouped launch's bodies).  Round 4 measured 32 at +0.2 ms per round on the six-term bf16 product (MFMA + conversion issue bound); on the fp16 product, which waits on memory for half of its wave life (profiles/r5_h3_64_pmc.txt), 32 is -0.6 ms: 33.73 against 34.32
-#endif
-template <int PIPE> constexpr int bf16x6_bk() { return PIPE == 2 ? 32 : PIPE == 0 ? RSCOTR_X6_BK0 : 16; }
-#ifndef RSCOTR_X6_D2
-#define RSCOTR_X6_D2 2
-#endif
-#ifndef RSCOTR_H3_VPM
-#define RSCOTR_H3_VPM 8
-#endif
-#ifndef RSCOTR_H3_DPM
-#define RSCOTR_H3_DPM 2
-#endif
-template <int PIPE> constexpr int bf16x6_depth() { return PIPE == 2 ? RSCOTR_X6_D2 : PIPE == 3 ? 3 : 1; }
+constexpr int X6_BK0 = 32;  // k per barrier pair of the one-stage loop (PIPE 0: the 128 x 128 kernels, the grouped launch's bodies).  Round 4 measured 32 at +0.2 ms per round on the six-term bf16 product (MFMA + conversion issue bound); on the fp16 product, which waits on memory for half of its wave life (profiles/r5_h3_64_pmc.txt), 32 is -0.6 ms: 33.73 against 34.32
+template <int PIPE> constexpr int bf16x6_bk() { return PIPE == 2 ? 32 : PIPE == 0 ? X6_BK0 : 16; }
+constexpr int X6_D2 = 2, H3_VPM = 8, H3_DPM = 2;
+template <int PIPE> constexpr int bf16x6_depth() { return PIPE == 2 ? X6_D2 : 1; }
 
 template <int BM, int BN, bool AKM, bool BKM, int PIPE, bool H16 = false>
 constexpr int bf16x6_lds_words() {
@@ -777,17 +762,8 @@ __device__ __forceinline__ void gemm_bf16x6_body(GemmParams& p, const int bx, co
       }
       // small terms first; term-major over the MT x NT accumulators (same sums, bit for bit): consecutive MFMAs write
       // DIFFERENT accumulators, so none waits for its predecessor's result (six back-to-back MFMAs on one accumulator are a
-      // dependent chain: RSCOTR_X6_CHAIN below restores that order for A/B builds)
+      // dependent chain)
       constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-#ifdef RSCOTR_X6_CHAIN
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int tm = 0; tm < 6; ++tm)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][PA[tm]], bf[j][PB[tm]], acc[i][j], 0, 0, 0);
-#else
 #pragma unroll
       for (int tm = 0; tm < 6; ++tm)
 #pragma unroll
@@ -795,15 +771,14 @@ __device__ __forceinline__ void gemm_bf16x6_body(GemmParams& p, const int bx, co
 #pragma unroll
           for (int j = 0; j < NT; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][PA[tm]], bf[j][PB[tm]], acc[i][j], 0, 0, 0);
-#endif
     }
   };
-  if (PIPE >= 2) {
+  if (PIPE == 2) {
     // Steady state without branches inside a step (the scheduler interleaves within one basic block): loads past the end
     // re-read the last tile, the last step stages it a second time into the idle LDS stage (its row sums times 0).
     constexpr int U = (D % 2 == 0) ? D : 2 * D;  // steps per unrolled round: register set and LDS stage indices static
     constexpr int NMFMA = MT * NT * (H16 ? 3 : 6) * (SBK / 16);
-    constexpr int VPM = H16 ? RSCOTR_H3_VPM : 4, DPM = H16 ? RSCOTR_H3_DPM : 1;  // VALU / DS writes the scheduler places behind each MFMA
+    constexpr int VPM = H16 ? H3_VPM : 4, DPM = H16 ? H3_DPM : 1;  // VALU / DS writes the scheduler places behind each MFMA
     // per-sample k scaling of a k-major A (weight gradients under DropPath / Mixup): always applied, so that a step stays
     // one basic block — without a scale vector every k reads the constant 1
     const float* ksp = (AKM && p.kscale) ? p.kscale : &bf16x6_one;
@@ -961,12 +936,8 @@ __device__ __forceinline__ void gemm_bf16x6_body(GemmParams& p, const int bx, co
   const bool one_extra = BM == 64 && !p.C2 &&
                          ((p.act == ACT_RELU_GRAD || p.act == ACT_GELU_GRAD) ? 1 : 0) + (p.resid ? 1 : 0) + (p.accumulate ? 1 : 0) == 1;
   // an activation (and / or the stored pre-activation) but no tensor to read: epilogue_noload16
-#ifdef RSCOTR_NO_NOLOAD  // (A/B builds: scripts/build_variant.sh)
-  const bool noload = false;
-#else
   const bool noload = !plain && (p.act == ACT_NONE || p.act == ACT_RELU || p.act == ACT_GELU) && !p.resid && !p.accumulate &&
                       !p.rowscale && !p.C2;
-#endif
   float amx = 0.f;
 #pragma unroll
   for (int i = 0; i < MT; ++i)
@@ -1385,45 +1356,39 @@ struct Split6Cfg {
 
 static Split6Cfg choose_split6(const GemmParams& p, int a_kmajor, int b_kmajor, int64_t ws_bytes) {
   Split6Cfg c{0, 1, p.K};
-  static const int on = getenv("RSCOTR_BF16X6") ? atoi(getenv("RSCOTR_BF16X6")) : 1;
-  static const long t128_min = getenv("RSCOTR_BF16X6_T128") ? atol(getenv("RSCOTR_BF16X6_T128")) : 512;
-  static const long t64_min = getenv("RSCOTR_BF16X6_T64") ? atol(getenv("RSCOTR_BF16X6_T64")) : 256;  // (round 4: 256 measures -0.3 ms per round on mtl512 against 512 — Swin stage-2 / -4 products move to the split product, flop share 0.85 -> 0.90; 384: -0.2; 192 and 128 lose 0.7.  It also re-routes the 2500-row stage-4 products of the 800 x 800 det step: that parity run passes with its tensors outside the 1e-3 tier explained by the fp64 anchor)
-  static const long dw_t128_min = getenv("RSCOTR_BF16X6_DW_T128") ? atol(getenv("RSCOTR_BF16X6_DW_T128")) : 24;
-  static const int k_min = getenv("RSCOTR_BF16X6_KMIN") ? atoi(getenv("RSCOTR_BF16X6_KMIN")) : 192;
-  static const int mid_split = getenv("RSCOTR_BF16X6_MIDSPLIT") ? atoi(getenv("RSCOTR_BF16X6_MIDSPLIT")) : 1;
-  static const int gelu_ok = getenv("RSCOTR_BF16X6_GELU") ? atoi(getenv("RSCOTR_BF16X6_GELU")) : 1;
-  static const long mid_t64 = getenv("RSCOTR_BF16X6_MID_T64") ? atol(getenv("RSCOTR_BF16X6_MID_T64")) : 96;  // (round 4: 96 takes the 512-row Swin stage-4 products with K >= 2304 (96 tiles, 6 k-slices): -0.25 ms per round against 128)
-  static const int mid_k = getenv("RSCOTR_BF16X6_MID_K") ? atoi(getenv("RSCOTR_BF16X6_MID_K")) : 1024;
-  static const int dw_ok = getenv("RSCOTR_BF16X6_DW") ? atoi(getenv("RSCOTR_BF16X6_DW")) : 1;
+  constexpr long t128_min = 512;
+  constexpr long t64_min = 256;  // (round 4: 256 measures -0.3 ms per round on mtl512 against 512 — Swin stage-2 / -4 products move to the split product, flop share 0.85 -> 0.90; 384: -0.2; 192 and 128 lose 0.7.  It also re-routes the 2500-row stage-4 products of the 800 x 800 det step: that parity run passes with its tensors outside the 1e-3 tier explained by the fp64 anchor)
+  constexpr long dw_t128_min = 24;
+  constexpr int k_min = 192;
+  constexpr long mid_t64 = 96;  // (round 4: 96 takes the 512-row Swin stage-4 products with K >= 2304 (96 tiles, 6 k-slices): -0.25 ms per round against 128)
+  constexpr int mid_k = 1024;
   // Measured on the step (profiles/r2_gemm_census.txt against profiles/history/r1_s7_gemm_census_fp32.txt): the split
   // product wins where the MFMA work dominates — the encoder FFN products (117 -> 85 us, 125 -> 100 us), their weight
   // gradients (124 -> 75 us), the 10880- / 2048-row products with K >= 256 (5-15 %) — and loses on small outputs (256 x 256
   // weight gradients: 22.6 -> 32.5 us: too few tiles to hide the staging), on K < 192 (conversion not amortised) and where
   // the epilogue's memory traffic bounds the launch anyway.
-  static const int edge_ok = getenv("RSCOTR_BF16X6_EDGE") ? atoi(getenv("RSCOTR_BF16X6_EDGE")) : 1;
-  if (!on || !p.vecA || !p.vecB || p.K % 4 || p.K < k_min || p.M < 64 || p.N < 64) return c;
+  if (!p.vecA || !p.vecB || p.K % 4 || p.K < k_min || p.M < 64 || p.N < 64) return c;
   // ragged shapes (M = 4 x 13 294 rows at 800 x 800, N = 96 / 288 columns of Swin stage 1, K = 53 176 of the 800 x 800 weight
   // gradients) take the EDGE instantiations: clamped loads, zeros past K, guarded stores; a k-major operand is read four
   // rows at a time, so its row count must be a multiple of 4
   const bool ragged = p.M % 64 || p.N % 64 || p.K % 16;
-  if (ragged && (!edge_ok || (a_kmajor && p.M % 4) || (b_kmajor && p.N % 4))) return c;
-  if (!gelu_ok && (p.act == ACT_GELU || p.act == ACT_GELU_GRAD || p.pre)) return c;
+  if (ragged && ((a_kmajor && p.M % 4) || (b_kmajor && p.N % 4))) return c;
   const long t64 = (long)((p.M + 63) / 64) * ((p.N + 63) / 64);
   const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
   // (a 128-wide tile on a ragged edge wastes up to half a tile per row / column of tiles: only where that is < 1/8 of the work)
   const bool fit128 = (p.M % 128 == 0 || p.M >= 1024) && (p.N % 128 == 0 || p.N >= 1024);
   if (a_kmajor && b_kmajor) {  // weight gradients: small outputs, long reductions -> k-slices through slabs
-    if (!dw_ok || p.rowscale || p.K < 1024 || p.M % 128 || p.N % 128 || t128 < dw_t128_min) return c;
+    if (p.rowscale || p.K < 1024 || p.M % 128 || p.N % 128 || t128 < dw_t128_min) return c;
     const int bm = 128;
     const long tiles = t128;
     if (tiles > 2048) return c;
-    static const long dw_wgs = getenv("RSCOTR_BF16X6_DW_WGS") ? atol(getenv("RSCOTR_BF16X6_DW_WGS")) : 512;  // workgroups a k-sliced weight gradient aims at
+    constexpr long dw_wgs = 512;  // workgroups a k-sliced weight gradient aims at
     long sp = std::max<long>(1, std::min<long>((dw_wgs + tiles - 1) / tiles, p.K / 256));
     const int64_t per = ((int64_t)p.M * p.N + p.M) * 4;
     if (sp > 1) sp = std::min<long>(sp, ws_bytes / per);
     if (sp < 1) sp = 1;
     int klen = (int)((p.K + sp - 1) / sp);
-    klen = (klen + RSCOTR_X6_BK0 - 1) / RSCOTR_X6_BK0 * RSCOTR_X6_BK0;
+    klen = (klen + X6_BK0 - 1) / X6_BK0 * X6_BK0;
     c.bm = bm; c.klen = klen; c.splits = (p.K + klen - 1) / klen;
     if (c.splits == 1) c.klen = p.K;
     return c;
@@ -1431,10 +1396,10 @@ static Split6Cfg choose_split6(const GemmParams& p, int a_kmajor, int b_kmajor, 
   if (p.kscale) return c;
   if (fit128 && t128 >= t128_min) c.bm = 128;
   else if (t64 >= t64_min && p.K <= 4096) c.bm = 64;
-  else if (mid_split && t64 >= mid_t64 && p.K >= mid_k) {
+  else if (t64 >= mid_t64 && p.K >= mid_k) {
     // mid-size outputs with a long reduction (Swin stage 3: 2048 x 384 x 1536): too few 64 x 64 tiles for the chip, so the
     // reduction is cut into k-slices whose slabs the combine launch sums and runs the epilogue on
-    static const int mid_kslice = getenv("RSCOTR_BF16X6_MID_KSLICE") ? atoi(getenv("RSCOTR_BF16X6_MID_KSLICE")) : 256;  // shortest k-slice
+    constexpr int mid_kslice = 256;  // shortest k-slice
     long sp = std::min<long>((512 + t64 - 1) / t64, p.K / mid_kslice);
     const int64_t per = ((int64_t)p.M * p.N + p.M) * 4;
     sp = std::min<long>(sp, ws_bytes / per);
@@ -1888,7 +1853,7 @@ static std::atomic<int> g_gemm_prec{[] {
   const char* e = getenv("RSCOTR_GEMM_PREC");
   if (e && (!strcmp(e, "fp32") || !strcmp(e, "0"))) return 0;
   if (e && (!strcmp(e, "bf16x6") || !strcmp(e, "3"))) return 3;
-  return RSCOTR_GEMM_PREC_DEFAULT;
+  return GEMM_PREC_DEFAULT;
 }()};
 
 template <typename Kern>
@@ -1938,13 +1903,8 @@ static void launch_gemm_cfg(const GemmParams& p, int a_kmajor, int b_kmajor, dim
 
 // Wavefront groups per workgroup for a launch of `wgs` workgroups with `nk` k-tiles each: short grids leave
 // most CUs idle, so the k loop of each tile is spread over 2 or 4 groups.
-static int choose_kgroups(long wgs, long nk, bool has_rowsum) {
-  static const char* force = getenv("RSCOTR_GEMM_KGROUPS");
-  static const int rs_ok = getenv("RSCOTR_GEMM_KG_ROWSUM") ? atoi(getenv("RSCOTR_GEMM_KG_ROWSUM")) : 1;
-  if (has_rowsum && !rs_ok) return 1;
-  if (force) return atoi(force) == 4 ? 4 : (atoi(force) == 2 ? 2 : 1);
-  static const long kg4_max = getenv("RSCOTR_GEMM_KG4_MAX") ? atol(getenv("RSCOTR_GEMM_KG4_MAX")) : 256;
-  static const long kg2_max = getenv("RSCOTR_GEMM_KG2_MAX") ? atol(getenv("RSCOTR_GEMM_KG2_MAX")) : 768;
+static int choose_kgroups(long wgs, long nk) {
+  constexpr long kg4_max = 256, kg2_max = 768;
   if (wgs <= kg4_max && nk >= 8) return 4;
   if (wgs <= kg2_max && nk >= 4) return 2;
   return 1;
@@ -1952,10 +1912,9 @@ static int choose_kgroups(long wgs, long nk, bool has_rowsum) {
 
 // The low-latency kernel's domain: small outputs, short reductions, no per-sample scaling (those are Swin products).
 static bool small_gemm_ok(const GemmParams& p, int a_kmajor, int b_kmajor, long nbatch) {
-  static const int on = getenv("RSCOTR_GEMM_SMALL") ? atoi(getenv("RSCOTR_GEMM_SMALL")) : 1;
-  static const long max_tiles = getenv("RSCOTR_GEMM_SMALL_TILES") ? atol(getenv("RSCOTR_GEMM_SMALL_TILES")) : 512;
-  static const int max_k = getenv("RSCOTR_GEMM_SMALL_K") ? atoi(getenv("RSCOTR_GEMM_SMALL_K")) : 512;
-  if (!on || p.K % 8 || p.K < 32 || p.rowscale || p.kscale) return false;
+  constexpr long max_tiles = 512;
+  constexpr int max_k = 512;
+  if (p.K % 8 || p.K < 32 || p.rowscale || p.kscale) return false;
   if ((!a_kmajor && !p.vecA) || (!b_kmajor && !p.vecB)) return false;
   const long tiles = (long)((p.M + 31) / 32) * ((p.N + 31) / 32);
   // a handful of output tiles with a longer reduction (the classifier's fc: 2 x 45 x 768) ran as ONE workgroup of the tiled
@@ -1990,15 +1949,13 @@ struct DwCfg {
 };
 
 static DwCfg choose_dw_direct(int M, int N, int K) {
-  static const int on = getenv("RSCOTR_GEMM_DW_DIRECT") ? atoi(getenv("RSCOTR_GEMM_DW_DIRECT")) : 1;
   // Measured on the step (profiles/README.md, trip 37): wins where the 64x64 tiling pads badly and the reduction is
   // very long (Swin stage 1: 288x96, 96x384, 384x96 over 32768 tokens: 104 / 80 / 77 us -> 67 / 68 / 69 us); loses on
   // the 256-wide and stage 2-3 gradients (one 24-load block in flight per wavefront is latency-bound below ~K = 16k).
-  static const int max_tiles = getenv("RSCOTR_GEMM_DW_TILES") ? atoi(getenv("RSCOTR_GEMM_DW_TILES")) : 4;
-  static const int min_k = getenv("RSCOTR_GEMM_DW_MINK") ? atoi(getenv("RSCOTR_GEMM_DW_MINK")) : 16384;
-  static const long target = getenv("RSCOTR_GEMM_DW_TARGET") ? atol(getenv("RSCOTR_GEMM_DW_TARGET")) : 256;
+  constexpr int max_tiles = 4, min_k = 16384;
+  constexpr long target = 256;
   DwCfg c{0, 0, 0, 0, 0};
-  if (!on || K < min_k || M < 8 || N < 8) return c;
+  if (K < min_k || M < 8 || N < 8) return c;
   // least padded of 96x96, 64x128, 128x64 wave tiles
   const int cand[3][2] = {{3, 3}, {2, 4}, {4, 2}};
   long best = -1;
@@ -2035,8 +1992,7 @@ static void launch_splitk_reduce(const GemmParams& p, const float* workspace, hi
   const int blocks = (int)std::min<long>((std::max<long>(work, M) + 255) / 256, 2048);
   ProfScope prof(PROF_HBM, (p.splits + 1.0 + (p.resid ? 1.0 : 0.0) + (p.aux ? 1.0 : 0.0) + (p.accumulate ? 1.0 : 0.0)) * 4.0 * total, s,
                  "rscotr::gemm_splitk_reduce_kernel");
-  static const int sg_ok = getenv("RSCOTR_GEMM_REDUCE_SG") ? atoi(getenv("RSCOTR_GEMM_REDUCE_SG")) : 1;
-  if (vec && sg_ok && p.splits >= 8 && blocks < 512 && (work + 63) / 64 * 256 >= M)
+  if (vec && p.splits >= 8 && blocks < 512 && (work + 63) / 64 * 256 >= M)
     gemm_splitk_reduce_sg_kernel<<<(unsigned)((work + 63) / 64), 256, 0, s>>>(p);
   else if (vec) gemm_splitk_reduce_kernel<true><<<blocks, 256, 0, s>>>(p);
   else gemm_splitk_reduce_kernel<false><<<blocks, 256, 0, s>>>(p);
@@ -2053,25 +2009,12 @@ struct GemmCfg {
   long splits;
 };
 
-static bool cfg_built(int BM, int BN) {
-  return (BM == 64 && BN == 64) || (BM == 128 && (BN == 32 || BN == 64));
-}
-
 // Tile / split choice.  The grid must cover 256 CUs a few times over (3 workgroups per CU are
 // resident): prefer the largest tile that still gives >= 512 tiles, then smaller tiles, then split K
 // (>= 16 k-tiles per split) through caller-provided slabs.
 static GemmCfg choose_cfg(int M, int N, int K) {
-  static const char* force = getenv("RSCOTR_GEMM_FORCE");  // "BM,BN,splits" — tuning only
   GemmCfg c;
-  if (force) {
-    int bm = 0, bn = 0, sp = 0;
-    if (sscanf(force, "%d,%d,%d", &bm, &bn, &sp) == 3 && cfg_built(bm, bn)) {
-      c.BM = bm; c.BN = bn;
-      c.splits = sp > 0 ? std::min<long>(sp, std::max(1, K / GEMM_BK)) : 1;
-      return c;
-    }
-  }
-  // Measured on MI355X over the step's shapes (scripts/tune_gemm.py, scripts/lab/gemm_lab.hip,
+  // Measured on MI355X over the step's shapes (a tile sweep of round 1, scripts/lab/gemm_lab.hip,
   // profiles/history/r1_gemm_tuning.md): 64x64 tiles (8 resident workgroups per CU) win on nearly every shape;
   // 128x64 wins on the wide, tall products of the encoder FFN (N >= 1024, >= 1360 tiles of 128x64).
   c.BM = 64; c.BN = 64;
@@ -2083,7 +2026,7 @@ static GemmCfg choose_cfg(int M, int N, int K) {
   // K is cut (>= 256 elements per slice) until the grid holds ~2 workgroups per CU (each then runs 2 k-groups:
   // 512 workgroups x 2 groups measured equal to 1024 x 1 with half the slab traffic).
   c.splits = 1;
-  static const long split_target = getenv("RSCOTR_GEMM_SPLIT_TARGET") ? atol(getenv("RSCOTR_GEMM_SPLIT_TARGET")) : 512;
+  constexpr long split_target = 512;
   if (t < 512 && K >= 1024) {
     long sp = (split_target + t - 1) / t;
     sp = std::min<long>(sp, K / 256);
@@ -2179,7 +2122,7 @@ extern "C" int rscotr_gemm_f32_rb(const float* A, const float* B, float* C, int 
 // split-product tiles with one k-slice: the products that may carry the ReLU gate as bits (ACT_RELU_BITS / ACT_RELU_GRAD_BITS)
 extern "C" int rscotr_gemm_relu_bits_ok(int M, int N, int K, int lda, int ldb, int a_kmajor, int b_kmajor) {
   if (M <= 0 || N <= 0 || K <= 0 || a_kmajor || g_gemm_prec.load(std::memory_order_relaxed) != 3) return 0;
-  if (M % 128 || N % 128 || K % RSCOTR_X6_BK0) return 0;
+  if (M % 128 || N % 128 || K % X6_BK0) return 0;
   GemmParams p{};
   p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = N;
   p.act = ACT_RELU;
@@ -2269,16 +2212,16 @@ static int gemm_f32_impl(const float* A, const float* B, float* C, int M, int N,
     const Split6Cfg sc = choose_split6(p, a_kmajor, b_kmajor, workspace ? workspace_bytes : 0);
     if (sc.bm) {
       p.tiles = ((M + sc.bm - 1) / sc.bm) * ((N + sc.bm - 1) / sc.bm);
-      const bool ragged = M % sc.bm || N % sc.bm || K % (sc.bm == 128 ? RSCOTR_X6_BK0 : 16);
+      const bool ragged = M % sc.bm || N % sc.bm || K % (sc.bm == 128 ? X6_BK0 : 16);
       p.splits = sc.splits; p.ksplit_len = sc.klen;
       p.slabs = sc.splits > 1 ? workspace : nullptr;
       p.rs_slabs = sc.splits > 1 ? workspace + sc.splits * (int64_t)M * N : nullptr;
       static const bool prof_shapes_6 = getenv("RSCOTR_PROF_SHAPES") != nullptr;
       const bool h3 = amax_a && amax_b && g_h3_on.load(std::memory_order_relaxed);
       p.amax_a = amax_a; p.amax_b = amax_b;
-      static const int pipelined = getenv("RSCOTR_BF16X6_PIPE") ? atoi(getenv("RSCOTR_BF16X6_PIPE")) : 1;  // bit 0: 64 x 64 (measured -0.45 ms / round), bit 1: 128 x 128 (measured slower on every layout of the step: +0.65 ms)
+      // the pipelined loop on 64 x 64 tiles measured -0.45 ms / round
       // B from its pre-split planes (rscotr_gemm_f32_rb; row-major by construction): the interior pipelined 64 x 64 fp16 kernel only
-      const bool use_planes = h3 && b_planes && !a_kmajor && !ragged && sc.bm == 64 && (pipelined & 1) && K % 32 == 0 && sc.klen % 32 == 0;
+      const bool use_planes = h3 && b_planes && !a_kmajor && !ragged && sc.bm == 64 && K % 32 == 0 && sc.klen % 32 == 0;
       if (use_planes) b_kmajor = 0;  // (what the kernel and its profile name see)
       char xname[112];
       if (prof_shapes_6) snprintf(xname, sizeof(xname), "M=%d N=%d K=%d %d%d %s-%d splits=%d", M, N, K, a_kmajor, b_kmajor, h3 ? "h3" : "bf16x6", sc.bm, sc.splits);
@@ -2293,7 +2236,7 @@ static int gemm_f32_impl(const float* A, const float* B, float* C, int M, int N,
         } else if (sc.bm == 128) {
           launch_h3<128, 0>(p, a_kmajor, b_kmajor, nwg, s);
         } else {
-          if ((pipelined & 1) && K % 32 == 0 && sc.klen % 32 == 0) {
+          if (K % 32 == 0 && sc.klen % 32 == 0) {
             if (use_planes) {  // no conversion of B in the loop
               p.B = reinterpret_cast<const float*>(b_planes);
               p.ldb = b_rpad;
@@ -2310,10 +2253,9 @@ static int gemm_f32_impl(const float* A, const float* B, float* C, int M, int N,
         else if (sc.klen % 32 == 0) launch_split6<64, 2, true>(p, a_kmajor, b_kmajor, nwg, s);
         else launch_split6<64, 1, true>(p, a_kmajor, b_kmajor, nwg, s);
       } else if (sc.bm == 128) {
-        if (pipelined & 2) launch_split6<128, 3>(p, a_kmajor, b_kmajor, nwg, s);
-        else launch_split6<128, 0>(p, a_kmajor, b_kmajor, nwg, s);
+        launch_split6<128, 0>(p, a_kmajor, b_kmajor, nwg, s);
       } else {
-        if ((pipelined & 1) && K % 32 == 0 && sc.klen % 32 == 0) launch_split6<64, 2>(p, a_kmajor, b_kmajor, nwg, s);
+        if (K % 32 == 0 && sc.klen % 32 == 0) launch_split6<64, 2>(p, a_kmajor, b_kmajor, nwg, s);
         else launch_split6<64, 1>(p, a_kmajor, b_kmajor, nwg, s);
       }
       if (int e = check_launch("rscotr_gemm_f32 (bf16x6)")) return e;
@@ -2333,10 +2275,6 @@ static int gemm_f32_impl(const float* A, const float* B, float* C, int M, int N,
     splits = std::min<long>(cfg.splits, workspace_bytes / (((int64_t)M * N + M) * 4));
     if (splits < 1) splits = 1;
   }
-  // a short grid with a moderately long reduction is better served by wavefront groups sharing the k loop
-  // inside the workgroup (no slabs, no combine launch) than by a split across workgroups
-  static const int kg_over_split = getenv("RSCOTR_GEMM_KG_OVER_SPLIT") ? atoi(getenv("RSCOTR_GEMM_KG_OVER_SPLIT")) : 0;
-  if (kg_over_split && !rowsum && K < 4096 && tiles <= 160 && (BM == 64 || BN == 32)) splits = 1;
   int klen = K;
   if (splits > 1) {
     klen = (int)((K + splits - 1) / splits);
@@ -2359,7 +2297,7 @@ static int gemm_f32_impl(const float* A, const float* B, float* C, int M, int N,
              BM == 128 && BN == 32 ? 4 : 2, BM == 128 && BN == 32 ? 1 : 2, a_kmajor ? "true" : "false",
              b_kmajor ? "true" : "false");
   ProfScope prof(PROF_GEMM, 2.0 * M * N * K, s, "%s", pname);
-  const int kg = choose_kgroups((long)grid.x, (klen + GEMM_BK - 1) / GEMM_BK, rowsum != nullptr);
+  const int kg = choose_kgroups((long)grid.x, (klen + GEMM_BK - 1) / GEMM_BK);
   if (BM == 64) launch_gemm_cfg<64, 64, 2, 2>(p, a_kmajor, b_kmajor, grid, s, kg);
   else if (BN == 32) launch_gemm_cfg<128, 32, 4, 1>(p, a_kmajor, b_kmajor, grid, s, kg);
   else launch_gemm_cfg<128, 64, 2, 2>(p, a_kmajor, b_kmajor, grid, s);
@@ -2420,9 +2358,8 @@ extern "C" int rscotr_gemm_f32_split_route(int M, int N, int K, int lda, int ldb
   const Split6Cfg sc = choose_split6(p, a_kmajor, b_kmajor, workspace_bytes);
   if (!sc.bm) return 0;
   // 2: the interior pipelined 64 x 64 kernel, which can take its B operand from pre-split planes (rscotr_gemm_f32_rb)
-  static const int pipelined = getenv("RSCOTR_BF16X6_PIPE") ? atoi(getenv("RSCOTR_BF16X6_PIPE")) : 1;
   const bool ragged = M % sc.bm || N % sc.bm || K % 16;
-  return (sc.bm == 64 && !ragged && !a_kmajor && (pipelined & 1) && K % 32 == 0 && sc.klen % 32 == 0) ? 2 : 1;
+  return (sc.bm == 64 && !ragged && !a_kmajor && K % 32 == 0 && sc.klen % 32 == 0) ? 2 : 1;
 }
 
 // Planes of weights for rscotr_gemm_f32_wplanes (layout: gemm_wplanes_kernel).  table: device (n, 8) int64 rows {W, planes, N,
@@ -2447,14 +2384,6 @@ extern "C" int rscotr_gemm_split_weights_h3(const int64_t* table, int n, int tot
 // Tile width and k-slices of the pre-split product: one 128 x 256 workgroup is resident per CU (86 KB of LDS), two 128 x 128
 // ones; the grid should be a whole number of such rounds over the 256 CUs (340 workgroups take as long as 512).
 static void wplanes_cfg(int M, int N, int K, int* bn_out, int* splits_out) {
-  static const char* force = getenv("RSCOTR_WPLANES_FORCE");  // "bn,splits" — tuning only
-  if (force) {
-    int b = 0, sp = 0;
-    if (sscanf(force, "%d,%d", &b, &sp) == 2 && (b == 128 || b == 256) && sp >= 1) {
-      *bn_out = b; *splits_out = (int)std::min<long>(sp, std::max(1, K / 128));
-      return;
-    }
-  }
   const long tm = (M + 127) / 128;
   const long smax = std::max<long>(1, std::min<long>(8, K / 256));
   double best = -1.0;
@@ -2480,8 +2409,7 @@ static void wplanes_cfg(int M, int N, int K, int* bn_out, int* splits_out) {
 // split-product kernels with their B operand from planes gained 15-28 % per dispatch and lost the round to the per-iteration
 // re-split of every weight — profiles/r4_planes_b_tiled.txt — and left the library in round 5.)
 static bool wplanes_classic(int M, int K) {
-  static const int min_m = getenv("RSCOTR_WPLANES_MIN_M") ? atoi(getenv("RSCOTR_WPLANES_MIN_M")) : 4096;
-  static const int min_k = getenv("RSCOTR_WPLANES_MIN_K") ? atoi(getenv("RSCOTR_WPLANES_MIN_K")) : 1024;
+  constexpr int min_m = 4096, min_k = 1024;
   return M >= min_m && K >= min_k;
 }
 
@@ -2683,7 +2611,7 @@ extern "C" int rscotr_gemm_f32_batched(const float* A, const float* B, float* C,
   p.tiles = (int)tiles;
   dim3 grid((unsigned)tiles, (unsigned)(nb0 * nb1 * ksplits), 1);
   hipStream_t s = (hipStream_t)stream;
-  const int kg = choose_kgroups((long)grid.x * grid.y, (p.K + GEMM_BK - 1) / GEMM_BK, false);
+  const int kg = choose_kgroups((long)grid.x * grid.y, (p.K + GEMM_BK - 1) / GEMM_BK);
   if (BM == 64) launch_gemm_cfg<64, 64, 2, 2>(p, a_kmajor, b_kmajor, grid, s, kg);
   else launch_gemm_cfg<128, 32, 4, 1>(p, a_kmajor, b_kmajor, grid, s, kg);
   if (int e = check_launch("rscotr_gemm_f32_batched")) return e;

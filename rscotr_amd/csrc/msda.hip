@@ -100,10 +100,6 @@ struct alignas(16) MsdaSampleB {
   int pad;
 };
 
-#ifndef RSCOTR_MSDA_FWD_DEDUP
-#define RSCOTR_MSDA_FWD_DEDUP 1  // (0: the per-lane set-up of rounds 1-4, for A/B builds)
-#endif
-
 // PREP (rscotr_msda_fwd_prep; L * P == 16): the kernel does the element-wise prologue of the attention module itself — the softmax
 // over the 16 logits of a (query, head) and the location arithmetic, by the 16 consecutive threads that stage its samples — and
 // leaves loc / attn in global memory for the backward, instead of reading what msda_prep_fwd_kernel wrote a launch earlier.
@@ -526,15 +522,12 @@ __global__ __launch_bounds__(256, P <= 4 && SCATTER == 0 ? 4 : 2) void msda_bwd_
 // Workspace (int32 words, per bh = b*H + h, NE = extended bins <= 2*Nk + 2*L):
 //   cnt[BH][NEmax], then per bh: start[NEmax+1] | keyrank[2*Nq*LP] | sorted[Nq*LP] x int4 | itemoff[Nk+1] |
 //   items[2*maxItems] | nitems
-// taps per work item of the pull kernel (RSCOTR_MSDA_CH overrides, for A/B runs)
-static int msda_ch() {
-  // 32, not 128: with 128 (fewer atomics, plan kernel 34 -> 18 us, round time unchanged) AND the bf16x3 weight-gradient route
-  // on, the 512^2 seg step lost parity whenever earlier processes had left data in device memory (140-440 of 459 gradient
-  // tensors outside the tight tier; 10-13 with either switch alone, 8 of 8 runs) — an unwritten word is read somewhere
-  // on that combination (both use the shared workspace); not found yet, so the long-standing value stays.
-  static const int v = [] { const char* e = getenv("RSCOTR_MSDA_CH"); const int x = e ? atoi(e) : 32; return x >= 8 ? x : 32; }();
-  return v;
-}
+// taps per work item of the pull kernel
+// 32, not 128: with 128 (fewer atomics, plan kernel 34 -> 18 us, round time unchanged) AND the bf16x3 weight-gradient route
+// on, the 512^2 seg step lost parity whenever earlier processes had left data in device memory (140-440 of 459 gradient
+// tensors outside the tight tier; 10-13 with either switch alone, 8 of 8 runs) — an unwritten word is read somewhere
+// on that combination (both use the shared workspace); not found yet, so the long-standing value stays.
+constexpr int MSDA_CH = 32;
 constexpr int MSDA_MAXL = 16;    // levels
 // LDS words of the bin histogram: the host only knows the bound NE <= 2 Nk + 2 L + 2 (the level shapes live on the
 // device); the kernels know NE = sum (H_l + 1)(W_l + 1) (~1.03 Nk for image pyramids) and all take the same
@@ -556,7 +549,7 @@ static MsdaWs msda_ws_layout(int BH, int Nk, int Nq, int L, int P) {
   const long S = (long)Nq * L * P;
   w.NEmax = 2 * Nk + 2 * L + 2;
   w.lds_words = std::min(w.NEmax, MSDA_LDS_WORDS);
-  w.CH = msda_ch();
+  w.CH = MSDA_CH;
   w.maxItems = (int)(Nk + (S * 4 + w.CH - 1) / w.CH + 1);
   w.C = (int)std::max<long>(1, std::min<long>(MSDA_MAXCHUNK, S / 1024));
   w.chunkcnt = ((long)BH * w.NEmax + 3) & ~3L;
@@ -966,9 +959,7 @@ constexpr int MSDA_T_TS = 16;      // bins per tile edge (at most)
 constexpr int MSDA_T_CW = 17;      // cells per tile edge
 constexpr int MSDA_T_CAP = 3072;   // kept records per sort + accumulate round (list entries: 8 bytes)
 constexpr int MSDA_T_TARGET = 10;  // mean run length (samples per bin and thread) a sample chunk is sized for
-#ifndef MSDA_T_OCC
-#define MSDA_T_OCC(D) ((D) <= 32 ? 3 : 2)
-#endif
+template <int D> constexpr int msda_t_occ() { return D <= 32 ? 3 : 2; }
 constexpr int MSDA_T_SEGB = 2048;  // blocks of the sample kernel per scan segment (their numbers live in LDS)
 
 struct MsdaTiles {
@@ -983,7 +974,7 @@ struct MsdaTiles {
 static bool msda_tiles_build(MsdaTiles* T, const int64_t* shapes_host, int L, int Nk, long SP, int D) {
   const int tsy_max = D >= 32 ? 8 : 16;  // MsdaTileGeom<D>::TSY
   if (!shapes_host || L < 1 || L > MSDA_T_MAXL) return false;
-  static const int target = [] { const char* e = getenv("RSCOTR_MSDA_TILE_RUN"); const int v = e ? atoi(e) : MSDA_T_TARGET; return v > 0 ? v : MSDA_T_TARGET; }();
+  constexpr int target = MSDA_T_TARGET;
   T->L = L;
   int nw = 0, tok = 0;
   for (int l = 0; l < L; ++l) {
@@ -1038,9 +1029,7 @@ struct MsdaTileGeom {
   static constexpr int TB = D >= 32 ? 2 : 1;
   static constexpr int CH = D / TB;
   static constexpr int V = CH / 4;                 // float4 per thread and row
-#ifndef MSDA_T_U16
-#define MSDA_T_U16 3  // (4 spilled 17 registers under the 168-register cap of three wavefronts per SIMD once the walk took balanced work items: +21 MiB of scratch writes per launch, encoder call 85 -> 78 us in the lab with 3)
-#endif
+  static constexpr int MSDA_T_U16 = 3;  // (4 spilled 17 registers under the 168-register cap of three wavefronts per SIMD once the walk took balanced work items: +21 MiB of scratch writes per launch, encoder call 85 -> 78 us in the lab with 3)
   static constexpr int U = CH <= 16 ? MSDA_T_U16 : 2;  // samples in flight per thread in the walk
   static constexpr int TSY = 256 / TB / MSDA_T_TS;  // bins per tile along y
   static constexpr int NBIN = MSDA_T_TS * TSY;
@@ -1069,26 +1058,12 @@ __device__ __forceinline__ int block_exclusive_scan_256(int v, int* scratch, int
   return before + inc - v;
 }
 
-// (lab builds only — scripts/lab/msda_lab.hip defines MSDA_T_PROFILE: shader-clock cycles per phase of every tile workgroup)
-#ifdef MSDA_T_PROFILE
-__device__ long long g_msda_tprof[1 << 16][8];
-#define MSDA_TP_INIT long long tp_last_ = clock64(), tp_acc_[5] = {0, 0, 0, 0, 0}; int tp_n_ = 0;
-#define MSDA_TP(i) { const long long t_ = clock64(); tp_acc_[i] += t_ - tp_last_; tp_last_ = t_; }
-#define MSDA_TP_N(n) tp_n_ += (n);
-#define MSDA_TP_DONE(level) if (threadIdx.x == 0 && blockIdx.x < (1 << 16)) { for (int i_ = 0; i_ < 5; ++i_) g_msda_tprof[blockIdx.x][i_] = tp_acc_[i_]; g_msda_tprof[blockIdx.x][5] = (level); g_msda_tprof[blockIdx.x][6] = tp_n_; g_msda_tprof[blockIdx.x][7] = 1; }
-#else
-#define MSDA_TP_INIT
-#define MSDA_TP(i)
-#define MSDA_TP_N(n)
-#define MSDA_TP_DONE(level)
-#endif
-
 // One 256-thread workgroup per (b, h, level, tile, chunk): see the header of this section.  A thread keeps the four tap
 // rows of ITS bin (its CH channels) in registers for the whole life of the workgroup: the walk over the sorted list needs
 // no barrier and no LDS accumulator — a thread reads the records of its bin in order, gathers each sample's grad_out row
 // (its part) once and feeds the four accumulators; the rows meet in the tile's cells only at the very end.
 template <int D, int P>
-__global__ __launch_bounds__(256, MSDA_T_OCC(D)) void msda_tile_kernel(const float* __restrict__ go, const float* __restrict__ loc,
+__global__ __launch_bounds__(256, msda_t_occ<D>()) void msda_tile_kernel(const float* __restrict__ go, const float* __restrict__ loc,
                                                         const float* __restrict__ attn,
                                                         const int* __restrict__ binw, const unsigned long long* __restrict__ mask,
                                                         float* __restrict__ part, MsdaTiles T, int Nq, int bshift,
@@ -1150,10 +1125,8 @@ __global__ __launch_bounds__(256, MSDA_T_OCC(D)) void msda_tile_kernel(const flo
   v2f a1[2 * V], a2[2 * V], a3[2 * V], a4[2 * V];  // the bin's four tap rows (this thread's channels)
   for (int i = tid; i < NCELL * D / 4; i += 256) reinterpret_cast<float4*>(acc)[i] = make_float4(0.f, 0.f, 0.f, 0.f);  // (ordered before the first add by the barriers of the scan)
 
-  MSDA_TP_INIT
   // sort the n kept records by bin (stable), then every thread adds the records of its bin to its accumulators
   auto flush = [&](int n) {
-    MSDA_TP(1) MSDA_TP_N(n)
     for (int i = tid; i < 4 * NBIN; i += 256) hist[i] = 0;
     __syncthreads();
     const int nw = ((n + 3) / 4 + 63) & ~63;  // records per wavefront (whole rounds of 64)
@@ -1175,7 +1148,6 @@ __global__ __launch_bounds__(256, MSDA_T_OCC(D)) void msda_tile_kernel(const flo
     __syncthreads();
     for (int i = i0 + lane; i < i1; i += 64) order[hist[w * NBIN + (lrec[i] & 255)] + rank[i]] = (unsigned short)i;
     __syncthreads();
-    MSDA_TP(2)
     // items: parts of at most R0 records per bin, at most NPAIR in all (n / R0 + non-empty bins <= NPAIR)
     const int runlen = tid < NBIN ? binstart[tid + 1] - binstart[tid] : 0;
     const int spare = max(NPAIR - __syncthreads_count(runlen > 0), 1);
@@ -1229,7 +1201,6 @@ __global__ __launch_bounds__(256, MSDA_T_OCC(D)) void msda_tile_kernel(const flo
         }
       }
     }
-    MSDA_TP(3)
     // The parts of one bin are consecutive items, i.e. neighbouring pairs.  (1) Inside a wavefront their rows are summed by a
     // suffix scan over the pairs (Hillis-Steele, shuffles; a fixed tree): the FIRST pair of a bin in each wavefront ends up
     // with the sum of the bin's parts in that wavefront.  (2) Those heads add their rows to the tile's cells — tap k of bin
@@ -1287,7 +1258,6 @@ __global__ __launch_bounds__(256, MSDA_T_OCC(D)) void msda_tile_kernel(const flo
         __syncthreads();
       }
     }
-    MSDA_TP(4)
   };
 
   // scan: only the blocks whose mask names this tile (kept in order in `blist`, a segment of MSDA_T_SEGB blocks at a
@@ -1314,7 +1284,6 @@ __global__ __launch_bounds__(256, MSDA_T_OCC(D)) void msda_tile_kernel(const flo
       cnt += t0 + t1 + t2 + t3;
     }
     __syncthreads();
-    MSDA_TP(0)
     auto index = [&](int rb) {  // first record of this thread in the round that starts at list position rb (-1: none)
       const int k = rb + slot;
       return k < cnt ? ((blk0 + seg + (int)blist[k]) << bshift) + off : -1;
@@ -1362,10 +1331,8 @@ __global__ __launch_bounds__(256, MSDA_T_OCC(D)) void msda_tile_kernel(const flo
   }
   __syncthreads();
   if (n > 0) flush(n);
-  MSDA_TP(1)
   float4* dst = reinterpret_cast<float4*>(part + ((long)bh * T.NW + e) * NCELL * D);
   for (int i = tid; i < NCELL * D / 4; i += 256) dst[i] = reinterpret_cast<const float4*>(acc)[i];
-  MSDA_TP(4) MSDA_TP_DONE(l)
 }
 
 // grad_value row of every token = the cells that alias it in the (at most four) tiles that hold it, every sample chunk, in
@@ -1471,7 +1438,7 @@ static void launch_fwd(const float* value, const int64_t* shapes, const int64_t*
         value, shapes, lsi, nullptr, nullptr, out, Nk, Nq, H, L, ntiles, *prep);
     return;
   }
-  if (RSCOTR_MSDA_FWD_DEDUP && shm_rec <= 48 * 1024 && (long)(Nk + 1) * H * D < (1l << 31)) {
+  if (shm_rec <= 48 * 1024 && (long)(Nk + 1) * H * D < (1l << 31)) {
     msda_fwd_kernel<D, P, true><<<dim3((unsigned)((long)B * ntiles * H)), dim3(256), shm_rec, s>>>(
         value, shapes, lsi, loc, attn, out, Nk, Nq, H, L, ntiles);
     return;
@@ -1525,14 +1492,8 @@ static void launch_bwd_sorted(const float* value, const int64_t* shapes, const i
   msda_plan_kernel<D><<<BH, 1024, hist_lds, s>>>(shapes, lsi, ws, W, gv, Nk, H, L);
   msda_fill_kernel<<<dim3(W.C, BH), 256, 0, s>>>(shapes, lsi, loc, attn, ws, W, Nq, H, L, P);
   constexpr int GPB = 256 / D;
-  static const int pull_u = [] { const char* e = getenv("RSCOTR_MSDA_PULL_U"); return e ? atoi(e) : 1; }();
-  if (pull_u == 1) {
-    const int bpb = (W.maxItems + GPB - 1) / GPB;
-    msda_pull_kernel<D, 1><<<dim3((unsigned)((long)BH * bpb)), 256, 0, s>>>(shapes, lsi, go, gv, ws, W, Nk, Nq, H, L, bpb);
-  } else {
-    const int bpb = (W.maxItems + 2 * GPB - 1) / (2 * GPB);
-    msda_pull_kernel<D, 2><<<dim3((unsigned)((long)BH * bpb)), 256, 0, s>>>(shapes, lsi, go, gv, ws, W, Nk, Nq, H, L, bpb);
-  }
+  const int bpb = (W.maxItems + GPB - 1) / GPB;
+  msda_pull_kernel<D, 1><<<dim3((unsigned)((long)BH * bpb)), 256, 0, s>>>(shapes, lsi, go, gv, ws, W, Nk, Nq, H, L, bpb);
   msda_chunk_combine_kernel<D><<<dim3(64, BH), 256, 0, s>>>(shapes, gv, ws, W, Nk, H, L);
 }
 
@@ -1584,7 +1545,7 @@ extern "C" int rscotr_msda_fwd(const float* value, const int64_t* spatial_shapes
 extern "C" int rscotr_msda_fused_ok(int Nk, int H, int D, int L, int P) {
   if (!(D == 16 || D == 32 || D == 64) || !(P == 1 || P == 2 || P == 4 || P == 8) || L < 1 || L > MSDA_MAXL || L * P != 16) return 0;
   const int QB = 4 * (kWave / (D / 4));
-  return RSCOTR_MSDA_FWD_DEDUP && (size_t)QB * L * P * sizeof(MsdaSample) <= 48 * 1024 && (long)(Nk + 1) * H * D < (1l << 31);
+  return (size_t)QB * L * P * sizeof(MsdaSample) <= 48 * 1024 && (long)(Nk + 1) * H * D < (1l << 31);
 }
 
 extern "C" int rscotr_msda_fwd_prep(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,

@@ -504,10 +504,7 @@ class DinoTransformerDecoder(TransformerLayerSequence):
             # query_pos = ref_point_head(...); the layer's first attention adds it to `output`: that sum leaves the MLP's last
             # epilogue as a second output (values only) instead of an element-wise add inside the attention wrapper
             head = [(m.weight, m.bias) for m in self.ref_point_head if isinstance(m, nn.Linear)]
-            if ops.STATE.pos_sum:
-                query_pos, q_sum = ops.mlp(pos_in, head, act='relu', sum_with=output)
-            else:
-                query_pos, q_sum = ops.mlp(pos_in, head, act='relu'), None
+            query_pos, q_sum = ops.mlp(pos_in, head, act='relu', sum_with=output)
             output = layer(output, None, values[lid], query_pos=query_pos, attn_masks=attn_mask, query_sum=q_sum,
                            key_padding_mask=key_padding_mask, reference_points=rp_in, **geom.kwargs())
             # three consumers of a layer's output: the next layer, the box branch, the shared norm

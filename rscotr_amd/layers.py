@@ -237,8 +237,7 @@ class BaseTransformerLayer(nn.Module):
         next_query_pos).  Sums are values only (no gradient of their own): every `norm` that is followed by an attention
         emits `norm(x) + query_pos` the same way instead of the attention wrapper launching an element-wise add."""
         norm_i = attn_i = ffn_i = 0
-        sums = ops.STATE.pos_sum
-        q_sum = query_sum if sums else None
+        q_sum = query_sum
         out_sum = None
         order = self.operation_order
         if attn_masks is None:
@@ -266,11 +265,10 @@ class BaseTransformerLayer(nn.Module):
                 last = j == len(order) - 1
                 nxt = order[j + 1] if not last else None
                 add = None
-                if sums:
-                    if nxt in ('self_attn', 'cross_attn'):
-                        add = pos_of(attn_i)
-                    elif last:
-                        add = next_query_pos
+                if nxt in ('self_attn', 'cross_attn'):
+                    add = pos_of(attn_i)
+                elif last:
+                    add = next_query_pos
                 if torch.is_tensor(add) and (add.shape == query.shape or add.shape[1:] == query.shape[1:]):
                     query, s_ = ops.layer_norm_sum(query, n.weight, n.bias, add)
                     if last:
@@ -283,7 +281,7 @@ class BaseTransformerLayer(nn.Module):
             elif op == 'cross_attn':
                 query = self.attentions[attn_i](query, key, value, None, query_pos=query_pos, key_pos=key_pos,
                                                 attn_mask=attn_masks[attn_i], key_padding_mask=key_padding_mask,
-                                                query_sum=q_sum, key_sum=key_sum if sums else None, **kwargs)
+                                                query_sum=q_sum, key_sum=key_sum, **kwargs)
                 attn_i += 1
                 q_sum = None
             else:

@@ -116,7 +116,7 @@ def msda(value, spatial_shapes, level_start_index, loc, attn):
 
 def _msda_fused_ok(Nk, H, D, L, P):
     """the prologue rides the sampling kernel's staging (rscotr_msda_fwd_prep): 16 samples per (query, head)"""
-    return STATE.msda_fused and bool(lib.rscotr_msda_fused_ok(Nk, H, D, L, P))
+    return bool(lib.rscotr_msda_fused_ok(Nk, H, D, L, P))
 
 
 def _msda_fwd_prep_raw(value, spatial_shapes, level_start_index, off, logit, ref, norm, L, P, ld_off, ld_logit):
@@ -230,7 +230,7 @@ class _MSDAAttn(Function):
         n_off, n_aw = H * L * P * 2, H * L * P
         # sampling_offsets | attention_weights as ONE product over the packed rows of the two weights (one small packing
         # launch instead of a second GEMM on the same operand; backward: one d(query) product over K = 3 n)
-        packed = STATE.msda_packed and b_off is not None and b_aw is not None and n_off % 4 == 0 and C % 4 == 0
+        packed = b_off is not None and b_aw is not None and n_off % 4 == 0 and C % 4 == 0
         if packed:
             n3 = n_off + n_aw
             wb = torch.empty(n3 * C + n3, dtype=torch.float32, device=x2.device)

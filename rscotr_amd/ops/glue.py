@@ -126,7 +126,7 @@ class _FanOut(Function):
 
 def fan_out(x, n):
     """-> n handles of x, one per consumer (see _FanOut); x itself when nothing is to be gained (n <= 2, no gradient)."""
-    if n <= 2 or not STATE.fan_out or not (torch.is_tensor(x) and x.requires_grad and x.is_cuda):
+    if n <= 2 or not (torch.is_tensor(x) and x.requires_grad and x.is_cuda):
         return [x] * n
     return list(_FanOut.apply(x, n))
 

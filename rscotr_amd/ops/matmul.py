@@ -108,7 +108,7 @@ class _WeightPlanesH:
     iteration is replayed)."""
 
     def __init__(self):
-        self.enabled = os.environ.get('RSCOTR_HPLANES', '1') != '0'
+        self.enabled = True
         self.version = 1
         self.entries, self.groups, self.tables = {}, {}, {}
         self.current = None
@@ -164,9 +164,6 @@ class _WeightPlanesH:
             hit = (DEFER._upload(np.asarray(rows, dtype=np.int64), dev), len(rows), first)
             if not (dev.type == 'cuda' and torch.cuda.is_current_stream_capturing()):
                 self.tables[stale] = hit  # (a table built inside a capture lives in the graph's private pool: not for later eager calls)
-        if os.environ.get('RSCOTR_HPLANES_DEBUG'):
-            import sys
-            print(f'[hplanes] group {self.current}: re-split {hit[1]} of {len(keys)} sets, {hit[2]} blocks (version {self.version})', file=sys.stderr, flush=True)
         lib.call('rscotr_gemm_split_weights_h3', hit[0].data_ptr(), hit[1], hit[2], _stream())
         for k in stale:
             self.entries[k]['version'] = self.version
@@ -233,7 +230,7 @@ class _DeferredCombine:
     BLOCK = 256 << 20
 
     def __init__(self):
-        self.enabled = os.environ.get('RSCOTR_DEFER_SPLITK', '1') != '0'
+        self.enabled = True
         self.blocks, self.cur, self.off = [], 0, 0
         self.entries, self.notify, self.cache = [], [], {}
         self.ln_entries, self.ln_cache = [], {}
@@ -244,9 +241,8 @@ class _DeferredCombine:
         self.pinned = set()
         # weight gradients with small outputs are not launched one by one: their operands are kept alive and ONE grouped
         # launch at the end of backward computes them all (rscotr_gemm_dw_group), then the combine below folds the slabs
-        self.group_enabled = os.environ.get('RSCOTR_DW_GROUP', '1') != '0'
-        self.group_x6 = int(os.environ.get('RSCOTR_DW_GROUP_X6', '1'))  # 0: every member on the fp32 pipe's 64 x 64 tiles
-        self.group_edge = int(os.environ.get('RSCOTR_DW_GROUP_EDGE', 48))  # members with min(M, N) >= this on the split product's 128 x 128 edge body
+        self.group_enabled = True
+        self.group_x6 = 1  # 0: every member on the fp32 pipe's 64 x 64 tiles
         self.group, self.group_keep, self.group_cache = [], [], {}
         self.group_amax, self.amax_cache = {}, {}  # operands of grouped problems whose value range is measured at the flush
         self.pinned_pool, self.pinned_live = [], []
@@ -254,13 +250,14 @@ class _DeferredCombine:
         self.wattn_entries, self.wattn_cache = [], {}
 
     MAX_TABLES = 64
-    GROUP_MAX_OUT = int(os.environ.get('RSCOTR_DW_GROUP_MAX', 160000))     # M * N of a grouped problem
-    GROUP_MAX_OUT_SHORT = int(os.environ.get('RSCOTR_DW_GROUP_MAX_SHORT', 2500000))  # ... with a short reduction (K <= GROUP_SHORT_K)
-    GROUP_SHORT_K = int(os.environ.get('RSCOTR_DW_GROUP_SHORT_K', 4096))
+    GROUP_MAX_OUT = 160000         # M * N of a grouped problem
+    GROUP_MAX_OUT_SHORT = 2500000  # ... with a short reduction (K <= GROUP_SHORT_K)
+    GROUP_SHORT_K = 4096
+    GROUP_EDGE = 48                # members with min(M, N) >= this on the split product's 128 x 128 edge body
 
     def grouped_size(self, M, N, K):
         return M * N <= self.GROUP_MAX_OUT or (K <= self.GROUP_SHORT_K and M * N <= self.GROUP_MAX_OUT_SHORT)
-    GROUP_TARGET_WGS = int(os.environ.get('RSCOTR_DW_GROUP_WGS', 4608))    # workgroups a grouped launch aims at
+    GROUP_TARGET_WGS = 4608        # workgroups a grouped launch aims at
 
     def _plan_group(self):
         """Slices and slab regions of the pending grouped problems -> ([(device table, problems, workgroups, variant)],
@@ -279,9 +276,9 @@ class _DeferredCombine:
             a, b, _, _, _, M, N, K, lda, ldb, _ = p[:11]
             ok = (self.group_x6 and K % 16 == 0 and K >= 512 and lda % 4 == 0 and ldb % 4 == 0 and a % 16 == 0 and b % 16 == 0
                   and M % 4 == 0 and N % 4 == 0)
-            # members with min(M, N) >= group_edge on the split product's 128 x 128 edge body (one launch), the rest on the fp32
+            # members with min(M, N) >= GROUP_EDGE on the split product's 128 x 128 edge body (one launch), the rest on the fp32
             # pipe's 64 x 64 tiles
-            return 6 if ok and self.group_edge and min(M, N) >= abs(self.group_edge) else 0
+            return 6 if ok and min(M, N) >= self.GROUP_EDGE else 0
         kinds = [kind(p) for p in probs]
         tiles = [((M + 127) // 128) * ((N + 127) // 128) if k in (6, 7) else ((M + 63) // 64) * ((N + 63) // 64)
                  for k, (_, _, _, _, _, M, N, K, _, _, _, _, _) in zip(kinds, probs)]
@@ -320,10 +317,6 @@ class _DeferredCombine:
                     first += 8 * rows[b0][15]
                 launches.append((self._upload(np.asarray(rows, dtype=np.int64), dev), len(rows), first, variant,
                                  float(sum(2.0 * r[5] * r[6] * r[7] for r in rows))))
-                if os.environ.get('RSCOTR_DW_GROUP_DUMP'):  # (tuning aid: the problems of one grouped launch)
-                    print(f'[dw group] variant {variant}: {len(rows)} problems, {first} workgroups, k-slice target {klen_t}')
-                    for r in rows:
-                        print(f'    M={r[5]} N={r[6]} K={r[7]} klen={r[10]} splits={r[11]} rowsum={int(r[3] != 0)}')
         return launches, ents
 
     def prepare_capture(self, n=4):
@@ -580,7 +573,7 @@ def _try_defer_dw(A, B, out, M, N, K, lda, ldb, rowsum, kscale, krows_per, nws):
     if DEFER.group_enabled and DEFER.grouped_size(M, N, K) and K >= 16:
         # small output: joins the grouped launch at the end of backward (operands stay alive until then)
         sa = sb = 0
-        if (K >= 512 and K % 16 == 0 and M % 4 == 0 and N % 4 == 0 and min(M, N) >= abs(DEFER.group_edge) and DEFER.group_edge
+        if (K >= 512 and K % 16 == 0 and M % 4 == 0 and N % 4 == 0 and min(M, N) >= DEFER.GROUP_EDGE
                 and DEFER.group_x6):  # (a member of the split-product launch, DEFER._plan_group: it wants the value ranges)
             sa, sb = (DEFER.group_range(A, K, M, lda), DEFER.group_range(B, K, N, ldb)) if RANGES.enabled else (0, 0)
             lo_r, hi_r = RANGES.base, RANGES.base + 4 * RANGES.STRIDE
@@ -710,11 +703,11 @@ class _RangeOut:
     the end of every workgroup's life (~1 us per launch: profiles/r5_range_word_cost.txt), and only an output that a LATER product
     multiplies with needs the word: callers that know their consumer is a norm, an attention core, the sampling kernel or an
     element-wise merge pass `range_out=False` (ops.linear / ops.gemm).  A tensor that does reach a product without a word is
-    measured there (rscotr_amax_f32: correct, one launch; RSCOTR_RANGES_STATS=1 lists them).  RSCOTR_RANGE_OUT_ALL=1: every
-    product writes its word, as before."""
+    measured there (rscotr_amax_f32: correct, one launch; RSCOTR_RANGES_STATS=1 lists them).  `all = True`: every product
+    writes its word, as before."""
 
     def __init__(self):
-        self.all = os.environ.get('RSCOTR_RANGE_OUT_ALL', '0') == '1'
+        self.all = False
         self.skip_next = False  # set by ops.linear(range_out=False) for the forward of the node it creates
 
     def enabled_for(self, out):
@@ -733,7 +726,7 @@ class _ReluBits:
     split-product tiles, the forward leaves M * N / 8 bytes of gate words and the backward reads those instead of h."""
 
     def __init__(self):
-        self.enabled = os.environ.get('RSCOTR_RELU_BITS', '1') != '0'
+        self.enabled = True
         self.cache = {}
 
     def ok(self, M, N, K, N_next):
@@ -757,20 +750,17 @@ class _FusedFFN:
     gradients only; backward dH = (g W2) * act', dX = dH W1 (+ g) with the mirrored call.  Taken where both weights are
     parameters of the optimizer's arena (their planes and range words live there) and the value ranges are on."""
 
-    MIN_ROWS = int(os.environ.get('RSCOTR_FFN_FUSED_MIN_ROWS', 1024))
+    MIN_ROWS = 1024
     MODE = {(ACT_RELU, 0): 0, (ACT_RELU, 1): 1, (ACT_GELU, 0): 2, (ACT_GELU, 1): 3}
 
     def __init__(self):
-        self.enabled = os.environ.get('RSCOTR_FFN_FUSED', '1') != '0'
-        self.gelu = os.environ.get('RSCOTR_FFN_FUSED_GELU', '1') != '0'  # (the Swin route on its own switch: A/B runs)
-        self.ln = os.environ.get('RSCOTR_FFN_FUSED_LN', '1') != '0'      # (the norm in front of a Swin MLP as the launch's prologue)
+        self.enabled = True
+        self.ln = True  # (the norm in front of a Swin MLP as the launch's prologue)
         self.calls = 0
         self.ln_calls = 0
 
     def ok(self, x2, ws, act, out_scale, sum_with):
         if not self.enabled or not RANGES.enabled or len(ws) != 2 or act not in (ACT_RELU, ACT_GELU) or sum_with is not None:
-            return False
-        if act == ACT_GELU and not self.gelu:
             return False
         sink = STATE.grad_sink
         (H, C), (C2, H2) = ws[0].shape, ws[1].shape
@@ -842,14 +832,12 @@ class _FusedLinear:
     kernels re-stage the rows once per column tile.  Taken where the weight is a parameter of the optimizer's arena and the value
     ranges are on; the 256-wide 10880-row Linears of the encoder stay on the tiled kernel (measured: profiles/r6_ffn_lab.txt)."""
 
-    MIN_ROWS = int(os.environ.get('RSCOTR_LIN_FUSED_MIN_ROWS', 8192))
-    MAX_NARROW = int(os.environ.get('RSCOTR_LIN_FUSED_NARROW', 192))  # the smaller of (N, K) at most this
-    FEW_K = tuple(int(k) for k in os.environ.get('RSCOTR_LIN_FUSED_FEW_K', '384,768').split(','))
+    MIN_ROWS = 8192
+    MAX_NARROW = 192  # the smaller of (N, K) at most this
+    FEW_K = (384, 768)
 
     def __init__(self):
-        self.enabled = os.environ.get('RSCOTR_LIN_FUSED', '1') != '0'
-        self.ln = os.environ.get('RSCOTR_LIN_FUSED_LN', '1') != '0'
-        self.few = os.environ.get('RSCOTR_LIN_FUSED_FEW', '1') != '0'
+        self.enabled = True
         self.calls = 0
         self.ln_calls = 0
 
@@ -862,14 +850,14 @@ class _FusedLinear:
         # FEW rows with a wide reduction (Swin stages 3 / 4: 2048 x 384 -> 1152 / 384, 512 x 768 -> 2304 / 768, the neck's 1x1
         # convolutions on them): one workgroup per (row tile, 256 columns), all of K staged once — 11 us against 17-27 for the tiled
         # kernels (fp32 pipe at 96-192 workgroups).  The decoders' K = 256 products stay where they are (measured: +1.35 ms per round)
-        few = self.few and 512 <= M < self.MIN_ROWS and K in self.FEW_K and N <= 3 * K
+        few = 512 <= M < self.MIN_ROWS and K in self.FEW_K and N <= 3 * K
         if not (tall or few):
             return False
         return sink.is_param_ptr(W.data_ptr()) and bool(lib.rscotr_lin_h3_ok(M, N, K))
 
     def ln_ok(self, lz, K):
         sink = STATE.grad_sink
-        return (self.ln and K in (96, 192, 384) and lz.w is not None and sink is not None and sink.is_param_ptr(lz.w.data_ptr())
+        return (K in (96, 192, 384) and lz.w is not None and sink is not None and sink.is_param_ptr(lz.w.data_ptr())
                 and (lz.b is None or sink.is_param_ptr(lz.b.data_ptr())))
 
     def run(self, x2, W, bias, tr, resid, want_y_range, xscale=None, yscale=None, rows_per=0, ln=None):

@@ -181,7 +181,7 @@ class Mask2FormerHead(nn.Module):
         qe = ops.fan_out(query_embed, nlay * n_att)
         # key + key_pos of a level is the same for every layer that attends to it: formed once per level (values only; the
         # attention's backward still returns d(key)); query + query_embed leaves the previous layer's last norm
-        key_sums = [torch.add(k.detach(), p) for k, p in zip(dec_in, dec_pos)] if ops.STATE.pos_sum else [None] * len(dec_in)
+        key_sums = [torch.add(k.detach(), p) for k, p in zip(dec_in, dec_pos)]
         q_sum = None
         for i in range(nlay):
             li = i % self.num_transformer_feat_level

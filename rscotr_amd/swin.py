@@ -96,7 +96,7 @@ class PatchMerging(nn.Module):
         self.reduction = nn.Linear(4 * in_channels, out_channels, bias=False)
 
     def forward(self, x, hw):
-        if ops.STATE.merge_norm and x.shape[-1] <= 512:  # unfold done by the norm's own loads / stores
+        if x.shape[-1] <= 512:  # unfold done by the norm's own loads / stores
             y, hw2 = ops.patch_merge_norm(x, hw, self.norm.weight, self.norm.bias)
         else:
             y, hw2 = ops.patch_merge_gather(x, hw)

@@ -7,10 +7,8 @@
 #include <cstring>
 #include <random>
 #include <vector>
-#ifndef MSDA_LAB_OLD
-#define MSDA_T_PROFILE 1
+#ifndef MSDA_LAB_OLD  // (-DMSDA_LAB_OLD -include <older msda.hip>: A/B against an earlier kernel)
 #include "../../rscotr_amd/csrc/msda.hip"
-#else  // -DMSDA_LAB_OLD -include <older msda.hip>: A/B against an earlier kernel (no phase table)
 #endif
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
@@ -114,26 +112,6 @@ int main(int argc, char** argv) {
     timeit([&] { msda_tile_kernel<32, 4><<<dim3(bh8 * (unsigned)T1.NW), 256, lds, s>>>(dgo, dloc, dattn, (int*)(w1 + W.binw), (unsigned long long*)(w1 + W.mask), part, T1, Nq, bshift, ntiles, H, BH); }, "  tile kernel");
     const int bpb = (Nk + 256 / (32 / 4) - 1) / (256 / (32 / 4));
     timeit([&] { msda_tile_combine_kernel<32><<<dim3(bh8 * (unsigned)bpb), 256, 0, s>>>(part, gv1, T1, Nk, H, BH, bpb); }, "  combine kernel");
-#ifndef MSDA_LAB_OLD
-    // per-level phase cycles of the tile workgroups (last launch)
-    static long long prof[1 << 16][8];
-    CK(hipMemcpyFromSymbol(prof, HIP_SYMBOL(g_msda_tprof), sizeof(prof)));
-    const unsigned nwg = bh8 * (unsigned)T1.NW;
-    printf("  tile kernel: %u workgroups, %zu bytes of LDS each; kilocycles per workgroup, mean (max): prep | scan | sort | walk | final | total | samples\n", nwg, lds);
-    for (int l = 0; l < L; ++l) {
-      double sum[6] = {0}, mx[6] = {0}; long cnt = 0; double ns = 0, nmx = 0;
-      for (unsigned i = 0; i < nwg && i < (1u << 16); ++i) {
-        if (!prof[i][7] || prof[i][5] != l) continue;
-        double tot = 0;
-        for (int k = 0; k < 5; ++k) { sum[k] += prof[i][k]; mx[k] = std::max(mx[k], (double)prof[i][k]); tot += prof[i][k]; }
-        sum[5] += tot; mx[5] = std::max(mx[5], tot); ns += prof[i][6]; nmx = std::max(nmx, (double)prof[i][6]); ++cnt;
-      }
-      if (!cnt) continue;
-      printf("    level %d (%4ld wgs):", l, cnt);
-      for (int k = 0; k < 6; ++k) printf(" %7.1f (%7.1f)", sum[k] / cnt / 1e3, mx[k] / 1e3);
-      printf("  %7.0f (%6.0f)\n", ns / cnt, nmx);
-    }
-#endif
   }
   // reference: the atomic scatter into a zeroed buffer
   CK(hipMemsetAsync(gv2, 0, value.size() * 4, s));

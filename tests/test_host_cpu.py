@@ -458,3 +458,28 @@ def test_rank_consistency_guard_tolerates_an_inexact_mean():
             assert abs(float(mean) - n) < 0.5 / world
             other = np.float32(mean + np.float32(1) / np.float32(world))  # one rank logs one key more
             assert not abs(float(other) - n) < 0.5 / world
+
+
+def test_environment_switches_are_the_readme_table_and_csrc_has_no_build_switches():
+    """Every RSCOTR_* variable the package reads is a row of README's table and every row is read; the library's sources hold
+    no conditional compilation (settled A/B switches are constants, lab variants live under scripts/lab)."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pkg = os.path.join(root, 'rscotr_amd')
+    read = set()
+    env_re = re.compile(r'''(?:environ\.get\(|environ\[|getenv\()\s*['"](RSCOTR_\w+)['"]''')
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(('.py', '.hip', '.cpp', '.h')):
+                with open(os.path.join(dirpath, f)) as fh:
+                    read |= set(env_re.findall(fh.read()))
+    with open(os.path.join(root, 'README.md')) as fh:
+        table = set(re.findall(r'^\| `(RSCOTR_\w+)` \|', fh.read(), flags=re.M))
+    assert read == table, (sorted(read - table), sorted(table - read))
+    csrc = os.path.join(pkg, 'csrc')
+    for f in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, f)) as fh:
+            for i, line in enumerate(fh, 1):
+                m = re.match(r'\s*#\s*(if|ifdef|ifndef|elif)\b(.*)', line)
+                # (include guards and compiler / architecture predefines only)
+                assert not m or re.fullmatch(r'\s*!?\s*(defined\s*\(?\s*)?__\w+\)?\s*(//.*)?', m.group(2)), f'{f}:{i}: {line.strip()}'
