@@ -703,6 +703,35 @@ int rscotr_img_aug_u8(const uint8_t* src, const int64_t* meta, const int32_t* ta
 int rscotr_seg_label_aug_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, int64_t* out, int B, int Hout,
                             int Wout, int reduce_zero_label, int pad_val, void* stream);
 
+/* ---- RandAugment on the device ---------------------------------------------------------------------------------------------
+ * Replaces mmcls RandAugment(policies=rand_increasing_policies, num_policies=2, total_level=10, magnitude_level=9,
+ * magnitude_std=0.5, hparams=dict(pad_val, interpolation='bicubic')) of configs/_base_/cls/resisc_swin_224.py:15-27 with the
+ * policies of configs/_base_/cls/rand_aug.py:2-42 (mmcv auto_contrast / imequalize / iminvert / posterize / solarize /
+ * adjust_color / adjust_contrast / adjust_brightness / adjust_sharpness / imrotate / imshear / imtranslate), which the
+ * reference runs per sample on CPU workers between RandomFlip and RandomErasing.  The batch takes three steps:
+ *   rscotr_img_frames_u8   the resample + flip half of rscotr_img_aug_u8 (same meta rows and tables; the colour, erasing
+ *                          and normalize fields are ignored) written as uint8 HWC BGR frames (B, H, W, 3); a sample's
+ *                          pixels outside its (out h, out w) are 0.  `frames` must not alias `src`.
+ *   rscotr_randaug_u8      ONE slot: every sample applies the operation of its meta row from frame `in` to frame `out`
+ *                          (both (B, H, W, 3) uint8, different buffers).  Called num_policies times, ping-pong.
+ *   rscotr_img_aug_u8      over identity nearest entries on the last frame: RandomErasing, Normalize, pad, CHW float32.
+ * meta: device (B, 16) int32 rows {op, w, h, integer parameter, float a (bits), float b (bits), warp table offset (int32
+ * elements into `warp`), warp interpolation (0 nearest, 1 bicubic), pad B, pad G, pad R, reserved x 5}; w <= W, h <= H
+ * (caller-checked: the entry cannot read device memory).  op: 0 copy, 1 AutoContrast, 2 Equalize, 3 Invert, 4 Posterize
+ * (integer parameter = 8 - bits), 5 Solarize (= ceil(thr)), 6 SolarizeAdd (= floor(magnitude)), 7 ColorTransform, 8 Contrast,
+ * 9 Brightness, 10 Sharpness (a = factor, b = float32(1 - factor)), 11 Rotate, 12 Shear, 13 Translate.
+ * warp: device int32; per warped sample {adelta[w], bdelta[w], X0[h], Y0[h]} of cv2.warpAffine's fixed point (AB_SCALE 1024,
+ * the inverse matrix in float64, round_delta folded into X0 / Y0), built by the host; taps outside (w, h) read the pad
+ * colour.  wtab: device (1024, 16) int16, cv2's bicubic remap weights (A = -0.75, each row sums to 32768), row
+ * (Y & 31) * 32 + (X & 31).  stats: device (B, 770) uint32 workspace, 8-byte aligned, required when need_stats != 0 (some
+ * sample's op is 1, 2 or 8): 3 x 256 histogram bins and the 64-bit sum of the cv2 grey value, zeroed by a memset node and
+ * accumulated with integer atomics (order-independent, so the result is bit-reproducible).  Launches: apply, preceded by
+ * memset + stats when need_stats. */
+int rscotr_img_frames_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, uint8_t* frames, int B, int H, int W,
+                         void* stream);
+int rscotr_randaug_u8(const uint8_t* in, uint8_t* out, const int32_t* meta, const int32_t* warp, const int16_t* wtab,
+                      uint32_t* stats, int need_stats, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@
 // (mmcv.imflip / imnormalize / impad, mmseg LoadAnnotations; the un-vendored mm* pipelines run these in NumPy/OpenCV
 // on float32 copies of the image: ~6 passes over the pixels per sample plus the collate copy).  Resizing, the
 // photometric and the erasing steps are the second pair of entries below (rscotr_img_aug_u8 / rscotr_seg_label_aug_u8);
-// decoding stays on the host and RandAugment is not implemented.
+// RandAugment is rscotr_img_frames_u8 below + randaug.hip; decoding stays on the host.
 //
 // HBM-bound: reads 3 B and writes 12 B per output pixel; one thread per output pixel x position, the three channel
 // planes written as coalesced float rows; source rows are read as bytes (3 consecutive bytes per thread: consecutive
@@ -234,6 +234,44 @@ __device__ __forceinline__ void photometric(int u[3], int flags, int hue_delta, 
     for (int c = 0; c < 3; ++c) u[c] = pm_convert(u[c], prm[1], 0.f);
 }
 
+// One pixel of the resized, flipped frame: output coordinate (x, y) of sample row `m` -> the uint8 BGR triplet, through
+// the host's per-axis tables.  Shared by img_aug_kernel and img_frames_kernel (the RandAugment path's first step).
+__device__ __forceinline__ void resample_u8(const uint8_t* __restrict__ src, const int64_t* __restrict__ m,
+                                            const int32_t* __restrict__ tables, int x, int y, int u[3]) {
+  const int cw = (int)m[4];
+  const long off = m[0], stride = m[3];
+  const int j = m[6] ? cw - 1 - x : x;
+  const int kx = (int)m[9], ky = (int)m[10], mode = (int)m[11];
+  const int32_t* tx = tables + m[7] + (long)j * (kx + 2);
+  const int32_t* ty = tables + m[8] + (long)y * (ky + 2);
+  const uint8_t* base = src + off;
+  if (mode == RESAMPLE_NEAREST) {
+    const uint8_t* p = base + (long)ty[0] * stride + (long)tx[0] * 3;
+    u[0] = p[0];
+    u[1] = p[1];
+    u[2] = p[2];
+  } else {
+    const int nx = tx[1], ny = ty[1];
+    const uint8_t* col = base + (long)tx[0] * 3;
+    int acc[3] = {0, 0, 0};
+    for (int a = 0; a < ny; ++a) {
+      const uint8_t* row = col + (long)(ty[0] + a) * stride;
+      int hs[3] = {0, 0, 0};
+      if (mode == RESAMPLE_PIL) hs[0] = hs[1] = hs[2] = 1 << 21;
+      for (int t = 0; t < nx; ++t) {
+        const int w = tx[2 + t];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) hs[c] += w * (int)row[t * 3 + c];
+      }
+      const int wy = ty[2 + a];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[c] += wy * (mode == RESAMPLE_PIL ? clip8_pil(hs[c]) : hs[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) u[c] = mode == RESAMPLE_PIL ? clip8_pil(acc[c] + (1 << 21)) : min(max((acc[c] + (1 << 21)) >> 22, 0), 255);
+  }
+}
+
 __global__ __launch_bounds__(256) void img_aug_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
                                                       const int32_t* __restrict__ tables,
                                                       const float* __restrict__ params, float* __restrict__ out,
@@ -245,38 +283,8 @@ __global__ __launch_bounds__(256) void img_aug_kernel(const uint8_t* __restrict_
   const int cw = (int)m[4], ch = (int)m[5];
   float v[3] = {0.f, 0.f, 0.f};  // mmcv Pad runs after Normalize with pad_val = 0
   if (y < ch && x < cw) {
-    const long off = m[0], stride = m[3];
-    const int j = m[6] ? cw - 1 - x : x;
-    const int kx = (int)m[9], ky = (int)m[10], mode = (int)m[11];
-    const int32_t* tx = tables + m[7] + (long)j * (kx + 2);
-    const int32_t* ty = tables + m[8] + (long)y * (ky + 2);
-    const uint8_t* base = src + off;
     int u[3];
-    if (mode == RESAMPLE_NEAREST) {
-      const uint8_t* p = base + (long)ty[0] * stride + (long)tx[0] * 3;
-      u[0] = p[0];
-      u[1] = p[1];
-      u[2] = p[2];
-    } else {
-      const int nx = tx[1], ny = ty[1];
-      const uint8_t* col = base + (long)tx[0] * 3;
-      int acc[3] = {0, 0, 0};
-      for (int a = 0; a < ny; ++a) {
-        const uint8_t* row = col + (long)(ty[0] + a) * stride;
-        int hs[3] = {0, 0, 0};
-        if (mode == RESAMPLE_PIL) hs[0] = hs[1] = hs[2] = 1 << 21;
-        for (int t = 0; t < nx; ++t) {
-          const int w = tx[2 + t];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) hs[c] += w * (int)row[t * 3 + c];
-        }
-        const int wy = ty[2 + a];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += wy * (mode == RESAMPLE_PIL ? clip8_pil(hs[c]) : hs[c]);
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) u[c] = mode == RESAMPLE_PIL ? clip8_pil(acc[c] + (1 << 21)) : min(max((acc[c] + (1 << 21)) >> 22, 0), 255);
-    }
+    resample_u8(src, m, tables, x, y, u);
     if (m[12]) photometric(u, (int)m[12], (int)m[13], params + (long)b * IMGAUG_PARAMS);
     const int ex = x - (int)m[14], ey = y - (int)m[15];
     if (ex >= 0 && ey >= 0 && ex < (int)m[16] && ey < (int)m[17]) {  // mmcls RandomErasing: patch overwrite
@@ -319,6 +327,24 @@ __global__ __launch_bounds__(256) void seg_label_aug_kernel(const uint8_t* __res
   out[((long)b * Hout + y) * Wout + x] = v;
 }
 
+// Step 1 of the RandAugment path (rscotr_img_frames_u8): the resample + flip half of img_aug_kernel, written as uint8 HWC BGR
+// frames (B, H, W, 3) for the in-place operations of randaug.hip; no colour stage, no erasing, no normalize.  Pixels outside
+// a sample's (out h, out w) are written 0.
+__global__ __launch_bounds__(256) void img_frames_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
+                                                         const int32_t* __restrict__ tables, uint8_t* __restrict__ frames,
+                                                         int H, int W) {
+  const int b = blockIdx.z, y = blockIdx.y;
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= W) return;
+  const int64_t* m = meta + (long)b * IMGAUG_META;
+  int u[3] = {0, 0, 0};
+  if (y < (int)m[5] && x < (int)m[4]) resample_u8(src, m, tables, x, y, u);
+  uint8_t* o = frames + (((long)b * H + y) * W + x) * 3;
+  o[0] = (uint8_t)u[0];
+  o[1] = (uint8_t)u[1];
+  o[2] = (uint8_t)u[2];
+}
+
 extern "C" int rscotr_img_aug_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, const float* params,
                                  float* out, int B, int Hout, int Wout, const float* mean3, const float* std3, int to_rgb,
                                  void* stream) {
@@ -345,4 +371,14 @@ extern "C" int rscotr_seg_label_aug_u8(const uint8_t* src, const int64_t* meta, 
   seg_label_aug_kernel<<<dim3((Wout + 255) / 256, Hout, B), 256, 0, (hipStream_t)stream>>>(src, meta, tables, out, Hout,
                                                                                          Wout, reduce_zero_label, pad_val);
   return check_launch("rscotr_seg_label_aug_u8");
+}
+
+extern "C" int rscotr_img_frames_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, uint8_t* frames, int B,
+                                    int H, int W, void* stream) {
+  if (int e = check_prep("rscotr_img_frames_u8", src, meta, frames, B, H, W)) return e;
+  if (B && H && W && !tables) return fail(RSCOTR_E_ARG, "rscotr_img_frames_u8: null pointer");
+  if (B && H && W && frames == src) return fail(RSCOTR_E_ARG, "rscotr_img_frames_u8: frames must not alias src");
+  if (B == 0 || H == 0 || W == 0) return RSCOTR_OK;
+  img_frames_kernel<<<dim3((W + 255) / 256, H, B), 256, 0, (hipStream_t)stream>>>(src, meta, tables, frames, H, W);
+  return check_launch("rscotr_img_frames_u8");
 }

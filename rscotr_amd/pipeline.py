@@ -6,7 +6,7 @@ Reference pipelines (configs/_base_/cls/resisc_swin_224.py:7-39, configs/_base_/
 configs/_base_/seg/potsdam_IRRG_all.py:8-19):
     decode (host) -> [Resize / RandomResizedCrop] -> RandomCrop window (seg) -> RandomFlip -> [PhotoMetricDistortion]
            -> [RandomErasing] -> Normalize(mean, std, to_rgb) -> Pad -> ImageToTensor / DefaultFormatBundle -> collate
-(bracketed: the optional stages below; RandAugment is not implemented).
+(bracketed: the optional stages below; mmcls RandAugment sits between RandomFlip and RandomErasing in the cls pipeline).
 Everything from the crop window on runs on the device; the host only draws the random decisions (with the same NumPy
 calls and in the same order as the mm* transforms, so a seeded run makes the same decisions) and uploads the raw bytes
 through one pinned staging buffer.  There is no CPU fallback: without the HIP library `collate` raises.
@@ -19,11 +19,21 @@ tables (source index, tap count and integer weights per output coordinate), so t
             (11-bit weights).  Parity with cv2 itself is unpinned: +-1 LSB expected (SIMD / IPP / exact-2x paths), unmeasured.
   'pillow'  mmcv backend='pillow', interpolation='bicubic': Pillow's ImagingResample (antialiased, 22-bit weights,
             uint8-clipped horizontal pass then vertical pass); equal to Pillow's own output.
-Label maps are resampled 'nearest' (mmcv: cv2 INTER_NEAREST).  RandAugment is not implemented (`build_collate`).
+Label maps are resampled 'nearest' (mmcv: cv2 INTER_NEAREST).
+
+RandAugment (`rand_augment=`, cls only, off by default; configs/_base_/cls/resisc_swin_224.py:15-27 with the policies of
+configs/_base_/cls/rand_aug.py) turns the one launch into a short sequence: `rscotr_img_frames_u8` writes the resized, flipped
+uint8 frames, `rscotr_randaug_u8` runs once per policy slot (each sample its own operation, ping frame to pong frame), and
+`rscotr_img_aug_u8` finishes over identity entries (RandomErasing, Normalize, pad).  The host draws from BOTH of mmcls's
+generators in its order (Python `random`: the policy choice and the gauss magnitudes; `numpy.random`: each transform's prob and
+sign draws) and builds the integer tables of the warps (cv2.warpAffine's fixed point).  The operations are restated from
+mmcv / OpenCV as remembered (tests/randaug_oracle.py spells them out): parity with mm* / cv2 is by reading and unpinned.
 """
 import ctypes
 import json
+import math
 import os
+import random
 
 import numpy as np
 import torch
@@ -40,6 +50,31 @@ PHOTOMETRIC = dict(brightness_delta=32, contrast_range=(0.5, 1.5), saturation_ra
 RANDOM_ERASING = dict(erase_prob=0.5, min_area_ratio=0.02, max_area_ratio=0.4, aspect_range=(3 / 10, 10 / 3), mode='const',
                       fill_color=(128, 128, 128), fill_std=None)  # mmcls RandomErasing's defaults
 RANDOM_RESIZED_CROP = dict(size=224, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.), max_attempts=10)
+# ---- RandAugment (include/rscotr.h: rscotr_randaug_u8's op codes, meta row and stats row) -------------------------------
+RA_OPS = dict(AutoContrast=1, Equalize=2, Invert=3, Posterize=4, Solarize=5, SolarizeAdd=6, ColorTransform=7, Contrast=8,
+              Brightness=9, Sharpness=10, Rotate=11, Shear=12, Translate=13)
+RA_META, RA_STATS = 16, 770
+RA_STATS_OPS = (RA_OPS['AutoContrast'], RA_OPS['Equalize'], RA_OPS['Contrast'])
+RA_SIGNED = ('Rotate', 'Shear', 'Translate', 'ColorTransform', 'Contrast', 'Brightness', 'Sharpness')  # random_negative
+RA_WARPS = dict(Rotate='nearest', Shear='bicubic', Translate='nearest')  # mmcls's default interpolation of each
+_RA_KEY = dict(Rotate='angle', Posterize='bits', Solarize='thr')  # the argument a magnitude lands in (else 'magnitude')
+# configs/_base_/cls/rand_aug.py:2-42 and the RandAugment arguments of configs/_base_/cls/resisc_swin_224.py:15-27
+RAND_INCREASING_POLICIES = [
+    dict(type='AutoContrast'), dict(type='Equalize'), dict(type='Invert'),
+    dict(type='Rotate', magnitude_key='angle', magnitude_range=(0, 30)),
+    dict(type='Posterize', magnitude_key='bits', magnitude_range=(4, 0)),
+    dict(type='Solarize', magnitude_key='thr', magnitude_range=(256, 0)),
+    dict(type='SolarizeAdd', magnitude_key='magnitude', magnitude_range=(0, 110)),
+    dict(type='ColorTransform', magnitude_key='magnitude', magnitude_range=(0, 0.9)),
+    dict(type='Contrast', magnitude_key='magnitude', magnitude_range=(0, 0.9)),
+    dict(type='Brightness', magnitude_key='magnitude', magnitude_range=(0, 0.9)),
+    dict(type='Sharpness', magnitude_key='magnitude', magnitude_range=(0, 0.9)),
+    dict(type='Shear', magnitude_key='magnitude', magnitude_range=(0, 0.3), direction='horizontal'),
+    dict(type='Shear', magnitude_key='magnitude', magnitude_range=(0, 0.3), direction='vertical'),
+    dict(type='Translate', magnitude_key='magnitude', magnitude_range=(0, 0.45), direction='horizontal'),
+    dict(type='Translate', magnitude_key='magnitude', magnitude_range=(0, 0.45), direction='vertical')]
+RAND_AUGMENT = dict(policies=RAND_INCREASING_POLICIES, num_policies=2, total_level=10, magnitude_level=9, magnitude_std=0.5,
+                    hparams=dict(pad_val=[104, 116, 124], interpolation='bicubic'))
 
 
 def _host_floats(v):
@@ -128,21 +163,143 @@ def rescale_size(w, h, scale):
     return _scale_size(w, h, sf), sf
 
 
+def ra_unsupported(cfg):
+    """Why the device stage cannot run this RandAugment config (a phrase naming the policy or interpolation), or None."""
+    pol = cfg.get('policies')
+    if not isinstance(pol, (list, tuple)) or len(pol) == 0:
+        return f'policies={pol!r} (a non-empty list of policy dicts is needed)'
+    hp = cfg.get('hparams') or {}
+    for p in pol:
+        typ = p.get('type') if isinstance(p, dict) else p
+        if typ not in RA_OPS:
+            return f'policy {typ!r}'
+        if typ in RA_WARPS:
+            interp = p.get('interpolation', hp.get('interpolation', RA_WARPS[typ]))
+            if interp not in ('nearest', 'bicubic'):
+                return f'{typ} with interpolation={interp!r} (nearest and bicubic are implemented)'
+    return None
+
+
+def _ra_config(cfg):
+    """The normalised settings: mmcls RandAugment's defaults filled in and `hparams` merged into the policies that accept
+    them and lack them (pad_val / interpolation: Rotate, Shear, Translate), pad_val as a BGR triple."""
+    cfg = dict(RAND_AUGMENT) if cfg is True else dict(cfg)
+    why = ra_unsupported(cfg)
+    if why is not None:
+        raise ValueError(f'rand_augment: {why}')
+    hp = dict(cfg.get('hparams') or {})
+    pols = []
+    for p in cfg['policies']:
+        p = dict(p)
+        if p['type'] in RA_WARPS:
+            p.setdefault('interpolation', hp.get('interpolation', RA_WARPS[p['type']]))
+            pv = p.get('pad_val', hp.get('pad_val', 128))
+            p['pad_val'] = tuple(int(v) for v in ((pv,) * 3 if isinstance(pv, (int, float)) else pv))
+            if len(p['pad_val']) != 3 or not all(0 <= v <= 255 for v in p['pad_val']):
+                raise ValueError(f'rand_augment: pad_val {pv!r} must be one or three values in [0, 255]')
+            if p['type'] != 'Rotate' and p.setdefault('direction', 'horizontal') not in ('horizontal', 'vertical'):
+                raise ValueError(f"rand_augment: {p['type']} direction {p['direction']!r}")
+        if ('magnitude_key' in p) != ('magnitude_range' in p):
+            raise ValueError(f"rand_augment: {p['type']} needs magnitude_key and magnitude_range together")
+        pols.append(p)
+    out = dict(policies=pols, num_policies=int(cfg.get('num_policies', 0)), magnitude_level=cfg.get('magnitude_level', 0),
+               total_level=cfg.get('total_level', 30), magnitude_std=cfg.get('magnitude_std', 0.), hparams=hp)
+    if out['num_policies'] < 0 or out['total_level'] <= 0:
+        raise ValueError('rand_augment: num_policies >= 0 and total_level > 0 expected')
+    return out
+
+
+def _ra_matrix(p, m, w, h):
+    """The FORWARD 2 x 3 matrix mmcv hands cv2.warpAffine (float64, row-major list of 6): imrotate's
+    getRotationMatrix2D(((w - 1) / 2, (h - 1) / 2), -angle, 1), imshear's and imtranslate's."""
+    if p['type'] == 'Rotate':
+        a = -m * math.pi / 180.0
+        al, be = math.cos(a), math.sin(a)
+        cx, cy = (w - 1) * 0.5, (h - 1) * 0.5
+        return [al, be, (1 - al) * cx - be * cy, -be, al, be * cx + (1 - al) * cy]
+    hor = p['direction'] == 'horizontal'
+    if p['type'] == 'Shear':
+        return [1.0, m, 0.0, 0.0, 1.0, 0.0] if hor else [1.0, 0.0, 0.0, m, 1.0, 0.0]
+    return [1.0, 0.0, m * w, 0.0, 1.0, 0.0] if hor else [1.0, 0.0, 0.0, 0.0, 1.0, m * h]
+
+
+def _ra_warp_table(M, w, h, bicubic):
+    """cv2.warpAffine without WARP_INVERSE_MAP: M inverted in float64 as OpenCV does, then the int32 coordinate tables
+    adelta[w] | bdelta[w] | X0[h] | Y0[h] (AB_SCALE = 1024, round_delta = 16 bicubic / 512 nearest folded into X0, Y0)."""
+    m0, m1, m2, m3, m4, m5 = [float(v) for v in M]
+    D = m0 * m4 - m1 * m3
+    D = 1.0 / D if D != 0 else 0.0
+    a11, a22 = m4 * D, m0 * D
+    m0, m1, m3, m4 = a11, m1 * -D, m3 * -D, a22
+    b1 = -m0 * m2 - m1 * m5
+    b2 = -m3 * m2 - m4 * m5
+    x, y = np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64)
+    rd = 16 if bicubic else 512
+    t = np.concatenate([np.rint(m0 * x * 1024), np.rint(m3 * x * 1024), np.rint((m1 * y + b1) * 1024) + rd,
+                        np.rint((m4 * y + b2) * 1024) + rd])
+    return np.clip(t, -2 ** 30, 2 ** 30).astype(np.int32)  # (a coordinate that large is outside any frame either way)
+
+
+_CUBIC_WTAB = None
+
+
+def cubic_weight_table():
+    """OpenCV's bicubic remap weights (initInterTab2D, INTER_CUBIC, fixed point): (1024, 16) int16, row ay * 32 + ax = the
+    4 x 4 products cy[k1] * cx[k2] of the float32 cubic coefficients (A = -0.75) at a / 32, times 32768, rounded half to even;
+    a row that does not sum to 32768 gives its deficit to the largest, or takes its excess from the smallest, of the 2 x 2 block
+    k1, k2 in (2, 3) -- OpenCV scans `ksize / 2 .. ksize / 2 + 1`, which for 4 taps is that block, not (1, 2); with (1, 2) the
+    row of a = (0, 0) would need the weight 32768, which int16 does not hold."""
+    global _CUBIC_WTAB
+    if _CUBIC_WTAB is not None:
+        return _CUBIC_WTAB
+    f = np.float32
+    A = f(-0.75)
+    x = (np.arange(32, dtype=np.float32) * f(1.0 / 32)).astype(f)
+    c = np.zeros((32, 4), f)
+    c[:, 0] = ((A * (x + f(1)) - f(5) * A) * (x + f(1)) + f(8) * A) * (x + f(1)) - f(4) * A
+    c[:, 1] = ((A + f(2)) * x - (A + f(3))) * x * x + f(1)
+    c[:, 2] = ((A + f(2)) * (f(1) - x) - (A + f(3))) * (f(1) - x) * (f(1) - x) + f(1)
+    c[:, 3] = f(1) - c[:, 0] - c[:, 1] - c[:, 2]
+    v = (c[:, None, :, None] * c[None, :, None, :]).astype(f)  # [ay, ax, k1, k2]
+    t = np.clip(np.rint(v * f(32768)), -32768, 32767).astype(np.int64).reshape(1024, 4, 4)
+    for row in t:
+        diff = int(row.sum()) - 32768
+        if diff:
+            lo = hi = (2, 2)
+            for k1 in (2, 3):
+                for k2 in (2, 3):
+                    if row[k1, k2] < row[lo]:
+                        lo = (k1, k2)
+                    elif row[k1, k2] > row[hi]:
+                        hi = (k1, k2)
+            row[hi if diff < 0 else lo] -= diff
+    _CUBIC_WTAB = t.reshape(1024, 16).astype(np.int16)
+    return _CUBIC_WTAB
+
+
+def _f32_bits(v):
+    return int(np.float32(v).view(np.int32))
+
+
 class DeviceCollate:
-    """Batch builder for one task.  `__call__(samples, rng=None)` takes the decoded samples of one batch
+    """Batch builder for one task.  `__call__(samples, rng=None, py_rng=None)` takes the decoded samples of one batch
     (dicts with `img`: HWC uint8 BGR ndarray, and per task `gt_label` | `gt_bboxes`, `gt_labels` | `gt_semantic_seg`:
     HW uint8) and returns the batch dict `MTL.train_step` consumes, tensors on `device`."""
 
     def __init__(self, task, device, img_norm_cfg=None, flip_prob=0.5, size_divisor=None, crop_size=None,
                  cat_max_ratio=1.0, reduce_zero_label=False, seg_pad_val=255, ignore_index=255, resize=None,
-                 random_resized_crop=None, photometric=None, random_erasing=None, resize_backend='cv2'):
+                 random_resized_crop=None, photometric=None, random_erasing=None, resize_backend='cv2',
+                 rand_augment=None):
         """Optional stages (None = off; any of them on routes the batch through `rscotr_img_aug_u8`):
         resize: mmseg / mmdet Resize, dict(img_scale=(long, short), ratio_range=None | (lo, hi), keep_ratio=True), or
                 mmcls Resize, dict(size=(h, w)) (a fixed size);
         random_resized_crop: mmcls RandomResizedCrop, dict(size, scale, ratio, max_attempts) (RANDOM_RESIZED_CROP);
         photometric: mmseg PhotoMetricDistortion, True or dict (PHOTOMETRIC);
         random_erasing: mmcls RandomErasing, dict (RANDOM_ERASING);
-        resize_backend: 'cv2' (bilinear) | 'pillow' (bicubic), the image resample of resize / random_resized_crop."""
+        resize_backend: 'cv2' (bilinear) | 'pillow' (bicubic), the image resample of resize / random_resized_crop;
+        rand_augment: mmcls RandAugment (task 'cls' only), True (RAND_AUGMENT, the reference's settings) or dict(policies,
+                num_policies, magnitude_level, total_level=30, magnitude_std=0., hparams); it routes the batch through
+                `rscotr_img_frames_u8` -> `rscotr_randaug_u8` per slot -> `rscotr_img_aug_u8`."""
         assert task in ('cls', 'det', 'seg')
         self.task, self.device = task, torch.device(device)
         cfg = dict(IMG_NORM if img_norm_cfg is None else img_norm_cfg)
@@ -163,7 +320,12 @@ class DeviceCollate:
                                                                              else {}))
         self.erasing = None if random_erasing is None else dict(RANDOM_ERASING, **random_erasing)
         self.resample = RESAMPLE_PIL if resize_backend == 'pillow' else RESAMPLE_LINEAR
-        self.augmented = any(x is not None for x in (self.resize, self.rrc, self.photometric, self.erasing))
+        if rand_augment is not None and rand_augment is not False and task != 'cls':
+            raise ValueError("rand_augment is for task 'cls' only: boxes and label maps do not follow its warps")
+        self.rand_augment = None if rand_augment is None or rand_augment is False else _ra_config(rand_augment)
+        self._ra_wtab = None  # device copy of cubic_weight_table() (uploaded once)
+        self.augmented = any(x is not None for x in (self.resize, self.rrc, self.photometric, self.erasing,
+                                                     self.rand_augment))
         self.skipped = []  # transforms build_collate was told to skip
         self._stage_done = None  # event after the last upload out of the staging buffer (augmented path)
 
@@ -296,10 +458,42 @@ class DeviceCollate:
             patch = np.clip(patch.astype(np.int32), 0, 255).astype(np.uint8)
         return left, top, w, h, patch
 
-    def draw(self, img_shape, seg, rng):
-        """Every random decision of one sample, in the reference's order (geometry, crop, flip, photometric, erasing):
-        a dict with the source rectangle `src` (x, y, w, h), the resized frame `rsz` (w, h), the window `win` (x0, y0, w, h)
-        in that frame, `flip`, `pm` (photometric draws or None) and `erase` (or None)."""
+    def _ra_draws(self, w, h, rng, py_rng):
+        """mmcls RandAugment.__call__ on a (h, w) frame -> (plan, chosen policies).  Python's generator: random.choices(policies,
+        k=num_policies), then per chosen policy with a magnitude_key one gauss(magnitude_level, magnitude_std) when std > 0.
+        NumPy's, per transform in order: rand() > prob -> unchanged; else, for the signed ones, rand() < random_negative_prob.
+        A plan entry is (op code, magnitude or None, applied, forward warpAffine matrix or None)."""
+        ra = self.rand_augment
+        if ra['num_policies'] == 0:
+            return [], []
+        chosen = py_rng.choices(ra['policies'], k=ra['num_policies'])
+        mags = []
+        for p in chosen:
+            if p.get('magnitude_key') is None:
+                mags.append(p.get(_RA_KEY.get(p['type'], 'magnitude')))
+                continue
+            level = ra['magnitude_level']
+            if ra['magnitude_std'] > 0:
+                level = py_rng.gauss(ra['magnitude_level'], ra['magnitude_std'])
+            level = min(ra['total_level'], max(0, level))
+            lo, hi = p['magnitude_range']
+            mags.append((level / ra['total_level']) * (hi - lo) + lo)
+        plan = []
+        for p, m in zip(chosen, mags):
+            typ = p['type']
+            applied = not (rng.rand() > p.get('prob', 0.5))
+            if typ not in ('AutoContrast', 'Equalize', 'Invert') and m is None:
+                raise ValueError(f'rand_augment: {typ} has neither a magnitude_key nor a fixed magnitude')
+            if applied and typ in RA_SIGNED and rng.rand() < p.get('random_negative_prob', 0.5):
+                m = -m
+            plan.append((RA_OPS[typ], m, applied, _ra_matrix(p, m, w, h) if applied and typ in RA_WARPS else None))
+        return plan, chosen
+
+    def draw(self, img_shape, seg, rng, py_rng=None):
+        """Every random decision of one sample, in the reference's order (geometry, crop, flip, photometric, RandAugment,
+        erasing): a dict with the source rectangle `src` (x, y, w, h), the resized frame `rsz` (w, h), the window `win`
+        (x0, y0, w, h) in that frame, `flip`, `pm` (photometric draws or None), `ra` (the RandAugment plan, `_ra_draws`; absent
+        when the stage is off) and `erase` (or None).  `py_rng`: the Python-side generator of RandAugment (default `random`)."""
         H, W = img_shape[:2]
         if self.rrc is not None:
             oy, ox, th, tw = self._rrc_params(H, W, rng)
@@ -326,13 +520,16 @@ class DeviceCollate:
         d = dict(src=src, rsz=rsz, win=win, flip=bool(rng.rand() < self.flip_prob), pm=None, erase=None)
         if self.photometric is not None:
             d['pm'] = self._photometric_draws(rng)
+        if self.rand_augment is not None:
+            d['ra'], d['ra_policies'] = self._ra_draws(win[2], win[3], rng, py_rng or random)
         if self.erasing is not None:
             d['erase'] = self._erasing_draws(win[3], win[2], rng)
         return d
 
-    def _upload(self, arrays):
+    def _upload(self, arrays, extra=0):
         """One host-to-device copy of `arrays` (16-byte aligned) out of the pinned staging buffer -> (device bytes, offsets).
-        The buffer is rewritten only after the previous copy out of it has completed."""
+        The buffer is rewritten only after the previous copy out of it has completed.  `extra` > 0: that many workspace bytes
+        follow the upload in the SAME device allocation (the RandAugment frames, reached by byte offsets from its start)."""
         offs = self._upload_offsets(arrays)
         total = max(_round_up(offs[-1] + arrays[-1].nbytes, 16), 16)
         if self._stage_done is not None:
@@ -342,11 +539,150 @@ class DeviceCollate:
         view = self._stage.numpy()
         for a, o in zip(arrays, offs):
             view[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
-        buf = self._stage[:total].to(self.device, non_blocking=True)
+        if extra:
+            buf = torch.empty(total + extra, dtype=torch.uint8, device=self.device)
+            buf[:total].copy_(self._stage[:total], non_blocking=True)
+        else:
+            buf = self._stage[:total].to(self.device, non_blocking=True)
         if self.device.type == 'cuda':
             self._stage_done = torch.cuda.Event()
             self._stage_done.record()
         return buf, offs
+
+    def _ra_meta_row(self, entry, p, w, h, warp_off):
+        """One rscotr_randaug_u8 meta row (include/rscotr.h) of a plan entry."""
+        op, m, applied, M = entry
+        row = [0, w, h] + [0] * (RA_META - 3)
+        if not applied:
+            return row
+        row[0] = op
+        typ = p['type']
+        if typ == 'Posterize':
+            bits = int(math.ceil(m))
+            if not 0 <= bits <= 8:
+                raise ValueError(f'rand_augment: Posterize bits {bits} outside [0, 8]')
+            row[3] = 8 - bits
+        elif typ == 'Solarize':  # v < thr for an integer v <=> v < ceil(thr)
+            row[3] = int(min(max(math.ceil(m), 0), 256))
+        elif typ == 'SolarizeAdd':  # uint8(min(v + m, 255)) = min(v + floor(m), 255) for m >= 0
+            if m < 0:
+                raise ValueError(f'rand_augment: SolarizeAdd magnitude {m} is negative')
+            row[3] = int(min(math.floor(m), 255))
+        elif typ in ('ColorTransform', 'Contrast', 'Brightness', 'Sharpness'):  # addWeighted(img, f, other, 1 - f, 0)
+            row[4], row[5] = _f32_bits(1 + m), _f32_bits(1 - (1 + m))
+        elif typ in RA_WARPS:
+            row[6], row[7] = warp_off, int(p['interpolation'] == 'bicubic')
+            row[8:11] = p['pad_val']
+        return row
+
+    def _call_randaug(self, samples, rng, py_rng):
+        """The cls batch with RandAugment: frames -> one `rscotr_randaug_u8` per slot -> `rscotr_img_aug_u8` over identity
+        entries on the last frame (erasing, normalize, pad).  One upload; the frames and the statistics table follow it in the
+        same device allocation."""
+        B = len(samples)
+        imgs = [s['img'] for s in samples]
+        ds = []
+        for img in imgs:
+            assert img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3, 'decoded HWC uint8 images expected'
+            ds.append(self.draw(img.shape, None, rng, py_rng))
+        Hf, Wf = max([d['win'][3] for d in ds], default=0), max([d['win'][2] for d in ds], default=0)
+        if self.crop_size:
+            Hout, Wout = self.crop_size
+        else:
+            Hout, Wout = Hf, Wf
+            if self.size_divisor:
+                Hout, Wout = _round_up(Hout, self.size_divisor), _round_up(Wout, self.size_divisor)
+        K = self.rand_augment['num_policies']
+        tabs, n_tab = [], 0
+
+        def add(t):
+            nonlocal n_tab
+            tabs.append(t)
+            n_tab += t.size
+            return n_tab - t.size, t.shape[1] - 2
+        geo = []
+        for img, d in zip(imgs, ds):
+            (sx, sy, sw, sh), (rw, rh), (x0, y0, cw, ch) = d['src'], d['rsz'], d['win']
+            assert 0 <= x0 and 0 <= y0 and x0 + cw <= rw and y0 + ch <= rh and cw <= Wout and ch <= Hout
+            mode = RESAMPLE_NEAREST if (sw, sh) == (rw, rh) else self.resample
+            xt, kx = add(_AXIS[mode](sw, rw, sx, x0, cw))
+            yt, ky = add(_AXIS[mode](sh, rh, sy, y0, ch))
+            geo.append((mode, xt, kx, yt, ky))
+        for t, dim in zip(tabs, [n for im in imgs for n in (im.shape[1], im.shape[0])]):
+            assert (t[:, 0] >= 0).all() and (t[:, 0] + t[:, 1] <= dim).all() and (t[:, 1] >= 1).all()
+        L = max(Hf, Wf, 1)
+        ident, _ = add(_axis_nearest(L, L, 0, 0, L))  # the last step reads the final frame as is, both axes
+        tables = np.concatenate([t.reshape(-1) for t in tabs])
+        # the slots' meta rows and the warps' coordinate tables
+        rmeta = np.zeros((max(K, 1), max(B, 1), RA_META), np.int32)
+        warps, n_warp, need_stats = [np.zeros(4, np.int32)], 4, [False] * K
+        for b, d in enumerate(ds):
+            cw, ch = d['win'][2], d['win'][3]
+            for k, (entry, p) in enumerate(zip(d['ra'], d['ra_policies'])):
+                off = 0
+                if entry[2] and entry[3] is not None:
+                    t = _ra_warp_table(entry[3], cw, ch, p['interpolation'] == 'bicubic')
+                    off, n_warp = n_warp, n_warp + t.size
+                    warps.append(t)
+                rmeta[k, b] = self._ra_meta_row(entry, p, cw, ch, off)
+                need_stats[k] = need_stats[k] or (entry[2] and entry[0] in RA_STATS_OPS)
+            for k in range(len(d['ra']), K):
+                rmeta[k, b, 1:3] = cw, ch
+        warp = np.concatenate(warps)
+        patches = [d['erase'][4] for d in ds if d['erase'] is not None]
+        params = np.zeros((max(B, 1), AUG_PARAMS), np.float32)
+        nimg = len(imgs)
+        # layout of the one upload: images | erasing patches | tables | params | meta | last step's meta | slot metas | warps;
+        # then, not uploaded: frame 0 | frame 1 | statistics
+        meta = np.zeros((max(B, 1), AUG_META), np.int64)
+        fmeta = np.zeros((max(B, 1), AUG_META), np.int64)
+        arrays = list(imgs) + patches + [tables, params, meta, fmeta, rmeta, warp]
+        offs = self._upload_offsets(arrays)
+        total = max(_round_up(offs[-1] + arrays[-1].nbytes, 16), 16)
+        fbytes = _round_up(B * Hf * Wf * 3, 16)
+        frame_off = [total, total + fbytes]
+        stats_off = total + 2 * fbytes
+        last = frame_off[K % 2]
+        pi = 0
+        for b, (img, d, g) in enumerate(zip(imgs, ds, geo)):
+            (x0, y0, cw, ch), (mode, xt, kx, yt, ky) = d['win'], g
+            meta[b, :12] = [offs[b], img.shape[0], img.shape[1], img.shape[1] * 3, cw, ch, int(d['flip']), xt, yt, kx, ky, mode]
+            fmeta[b, :12] = [last + b * Hf * Wf * 3, Hf, Wf, Wf * 3, cw, ch, 0, ident, ident, 1, 1, RESAMPLE_NEAREST]
+            if d['erase'] is not None:
+                ex, ey, ew, eh, patch = d['erase']
+                assert ex + ew <= cw and ey + eh <= ch
+                fmeta[b, 14:19] = [ex, ey, ew, eh, offs[nimg + pi]]
+                pi += 1
+        buf, offs = self._upload(arrays, extra=2 * fbytes + _round_up(B * RA_STATS * 4, 16))
+        ptr = buf.data_ptr()
+        p_tab, p_prm, p_meta, p_fmeta, p_rmeta, p_warp = [ptr + o for o in offs[-6:]]
+        if self._ra_wtab is None or self._ra_wtab.device != self.device:
+            self._ra_wtab = torch.from_numpy(cubic_weight_table()).to(self.device)
+        out = torch.empty((B, 3, Hout, Wout), dtype=torch.float32, device=self.device)
+        mean_keep, mean_p = _host_floats(self.mean)
+        std_keep, std_p = _host_floats(self.std)
+        stream = ops._stream()
+        lib.call('rscotr_img_frames_u8', ptr, p_meta, p_tab, ptr + frame_off[0], B, Hf, Wf, stream)
+        for k in range(K):
+            lib.call('rscotr_randaug_u8', ptr + frame_off[k % 2], ptr + frame_off[(k + 1) % 2],
+                     p_rmeta + k * max(B, 1) * RA_META * 4, p_warp, self._ra_wtab.data_ptr(), ptr + stats_off,
+                     int(need_stats[k]), B, Hf, Wf, stream)
+        lib.call('rscotr_img_aug_u8', ptr, p_fmeta, p_tab, p_prm, out.data_ptr(), B, Hout, Wout, mean_p, std_p,
+                 int(self.to_rgb), stream)
+        metas = []
+        for im, d in zip(imgs, ds):
+            (sx, sy, sw, sh), (rw, rh), (x0, y0, cw, ch) = d['src'], d['rsz'], d['win']
+            m = dict(ori_shape=im.shape, img_shape=(ch, cw, 3), pad_shape=(Hout, Wout, 3), flip=d['flip'],
+                     flip_direction='horizontal' if d['flip'] else None, scale_factor=1.0,
+                     img_norm_cfg=dict(mean=self.mean, std=self.std, to_rgb=self.to_rgb))
+            if self.resize is not None or self.rrc is not None:
+                m['scale_factor'] = np.array([rw / sw, rh / sh, rw / sw, rh / sh], dtype=np.float32)
+                m['keep_ratio'] = bool(self.resize is not None and self.resize.get('keep_ratio') and 'size' not in self.resize)
+            metas.append(m)
+        for m, d in zip(metas, ds):
+            m['rand_augment'] = d['ra']  # the plan that was applied (`_ra_draws`)
+        return dict(img=out, img_metas=metas,
+                    gt_label=torch.tensor([int(s['gt_label']) for s in samples], dtype=torch.int64, device=self.device))
 
     def _call_augmented(self, samples, rng):
         B = len(samples)
@@ -471,8 +807,10 @@ class DeviceCollate:
             o = _round_up(o + a.nbytes, 16)
         return offs
 
-    def __call__(self, samples, rng=None):
+    def __call__(self, samples, rng=None, py_rng=None):
         rng = rng or np.random
+        if self.rand_augment is not None:
+            return self._call_randaug(samples, rng, py_rng or random)
         if self.augmented:
             return self._call_augmented(samples, rng)
         B = len(samples)
@@ -549,7 +887,8 @@ def scale_boxes(bboxes, scale_factor, img_shape):
 
 
 # the three dataset configs' augmentation settings (configs/_base_/cls/resisc_swin_224.py:10-35,43-48,
-# configs/_base_/det/dior.py:13-18,24-33, configs/_base_/seg/potsdam_IRRG_all.py:10-18,24-31); RandAugment is left out
+# configs/_base_/det/dior.py:13-18,24-33, configs/_base_/seg/potsdam_IRRG_all.py:10-18,24-31); RandAugment's are RAND_AUGMENT above,
+# off by default (train_collate_for('cls', device, rand_augment=True) is the reference's whole cls recipe)
 CLS_ERASING = dict(erase_prob=0.25, mode='rand', min_area_ratio=0.02, max_area_ratio=1 / 3,
                    fill_color=IMG_NORM['mean'][::-1], fill_std=IMG_NORM['std'][::-1])
 
@@ -558,7 +897,8 @@ def train_collate_for(task, device, **kw):
     """The training pipelines' collate with the resampling and colour stages on the device:
     cls RandomResizedCrop(224, bicubic, pillow) + RandomFlip + RandomErasing; det keep-ratio Resize((1333, 800)) + RandomFlip
     + Pad(32); seg Resize((512, 512), ratio_range=(0.5, 2.0)) + RandomCrop(512, cat_max_ratio=0.75) + RandomFlip +
-    PhotoMetricDistortion + Pad(512, seg_pad_val=5).  Keyword arguments override these settings."""
+    PhotoMetricDistortion + Pad(512, seg_pad_val=5).  Keyword arguments override these settings; `rand_augment=True` adds the
+    reference's RandAugment (RAND_AUGMENT) to the cls pipeline."""
     if task == 'cls':
         cfg = dict(flip_prob=0.5, random_resized_crop=dict(size=224), resize_backend='pillow', random_erasing=CLS_ERASING)
     elif task == 'det':
@@ -589,10 +929,12 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
 
     Understood: LoadImageFromFile, LoadAnnotations (reduce_zero_label), Resize (mmseg / mmdet img_scale + ratio_range +
     keep_ratio; mmcls size + backend + interpolation), RandomResizedCrop, RandomCrop, RandomFlip, PhotoMetricDistortion,
-    RandomErasing, Normalize, Pad, ImageToTensor, ToTensor, DefaultFormatBundle, Collect and MultiScaleFlipAug (its single
-    scale and its transforms; flip=False).  Anything else (RandAugment among them) raises NotImplementedError naming it,
-    unless unsupported='skip': then it is left out and listed in `collate.skipped`, and the random stream no longer matches
-    the reference's (the skipped transform's draws are not made)."""
+    RandomErasing, Normalize, Pad, ImageToTensor, ToTensor, DefaultFormatBundle, Collect, MultiScaleFlipAug (its single
+    scale and its transforms; flip=False) and RandAugment when `policies` is a non-empty list of the 13 implemented types
+    (RA_OPS) whose warps ask for 'nearest' or 'bicubic'.  Anything else (a RandAugment with an empty list, another policy or
+    another interpolation among them) raises NotImplementedError naming it, unless unsupported='skip': then it is left out and
+    listed in `collate.skipped`, and the random stream no longer matches the reference's (the skipped transform's draws are
+    not made)."""
     assert unsupported in ('raise', 'skip')
     kw, skipped, norm = dict(flip_prob=0.0), [], None
 
@@ -649,10 +991,13 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
             if t.get('size') is not None and 'crop_size' not in kw:
                 raise NotImplementedError('Pad(size=...) without RandomCrop')
             kw['seg_pad_val'] = t.get('seg_pad_val', 255)
+        elif typ == 'RandAugment' and ra_unsupported(t) is None:
+            kw['rand_augment'] = t
         elif unsupported == 'skip':
             skipped.append(typ)
         else:
-            raise NotImplementedError(f'{typ} is not implemented by the device collate (build_collate(..., '
+            what = f'RandAugment: {ra_unsupported(t)}' if typ == 'RandAugment' else typ
+            raise NotImplementedError(f'{what} is not implemented by the device collate (build_collate(..., '
                                       f"unsupported='skip') leaves it out)")
     for t in pipeline_cfg:
         visit(t)
@@ -813,6 +1158,7 @@ class DeviceLoader:
     def __init__(self, dataset, collate, batch_size, shuffle=True, drop_last=True, seed=0, test_mode=False):
         self.dataset, self.collate, self.batch_size = dataset, collate, batch_size
         self.shuffle, self.drop_last, self.rng = shuffle, drop_last, np.random.RandomState(seed)
+        self.py_rng = random.Random(seed)  # RandAugment's second generator (mmcls draws its policies from `random`)
         # test_mode: dataset order, every sample, batches of {task, img, img_metas} only — what `engine.single_gpu_test` feeds
         # `model(return_loss=False, **data)` (the collate should be built with flip_prob = 0 and no crop)
         self.test_mode = test_mode
@@ -827,5 +1173,8 @@ class DeviceLoader:
         order = self.rng.permutation(len(self.dataset)) if self.shuffle else np.arange(len(self.dataset))
         for b in range(len(self)):
             idx = order[b * self.batch_size:(b + 1) * self.batch_size]
-            batch = self.collate([self.dataset[int(i)] for i in idx], self.rng)
+            if getattr(self.collate, 'rand_augment', None) is not None:
+                batch = self.collate([self.dataset[int(i)] for i in idx], self.rng, self.py_rng)
+            else:
+                batch = self.collate([self.dataset[int(i)] for i in idx], self.rng)
             yield dict(task=self.dataset.task, img=batch['img'], img_metas=batch['img_metas']) if self.test_mode else batch

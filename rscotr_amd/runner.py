@@ -6,6 +6,7 @@ Per iteration: batch = next(MultiDataLoader) -> model.train_step -> zero_grad ->
 schedule / logging.  Hook order is the reference's: zero_grad, backward, clip, step.
 """
 import contextlib
+import gc
 import os
 import time
 from collections import OrderedDict
@@ -258,8 +259,20 @@ class GraphedTask:
             self.opt.prepare_step(self.table)
             # thread_local: the RCCL watchdog thread polls its events while this thread captures; under the default
             # global mode that poll is "not permitted when stream is capturing" and kills the process group
-            with torch.cuda.graph(self.graph, stream=side, capture_error_mode='thread_local'):
-                self._body()
+            # torch.cuda.graph no longer collects garbage on entry (torch.compiler.config.force_cudagraph_gc is off by
+            # default since 2.9), so a cycle collection that falls inside the capture would run the destructors of whatever
+            # dead cycles earlier work left behind (pinned staging buffers, events, other graphs) from THIS thread, and the
+            # calls they make are not permitted while it captures: the process aborts.  Collect first, and keep the
+            # collector off until the capture has ended.
+            gc.collect()
+            gc_on = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(self.graph, stream=side, capture_error_mode='thread_local'):
+                    self._body()
+            finally:
+                if gc_on:
+                    gc.enable()
         except Exception:
             ops.DEFER.drop()
             ops.DEFER.forget_captured()
