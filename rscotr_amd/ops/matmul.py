@@ -472,18 +472,23 @@ class _DeferredCombine:
         self.group, self.group_keep = [], []
 
     def _flush_wattn(self):
-        """Partial rows of the window-attention backward passes (bias-table / pad-token gradients): one fold launch."""
+        """Partial rows of the window-attention backward passes (bias-table / pad-token gradients): one fold launch, or one
+        per round when a block's destinations are pending more than once (the same block twice in one pass, or passes
+        accumulated without a flush in between)."""
         sig = tuple(self.wattn_entries)
         hit = self.wattn_cache.get(sig)
         if hit is None:
             import numpy as np
-            rows, first = [], 0
-            for part, dt, db, heads, C, nrows in self.wattn_entries:
-                rows.append((part, dt, db, heads, C, nrows, first) + (0,) * 9)
-                first += heads
-            hit = (self._upload(np.asarray(rows, dtype=np.int64), self.blocks[0].device), len(rows), first)
+            hit = []
+            for ents in self._rounds(self.wattn_entries, lambda e: (e[1], e[2])):
+                rows, first = [], 0
+                for part, dt, db, heads, C, nrows in ents:
+                    rows.append((part, dt, db, heads, C, nrows, first) + (0,) * 9)
+                    first += heads
+                hit.append((self._upload(np.asarray(rows, dtype=np.int64), self.blocks[0].device), len(rows), first))
         self._remember(self.wattn_cache, sig, hit)
-        lib.call('rscotr_swin_wattn_flush', hit[0].data_ptr(), hit[1], hit[2], _stream())
+        for tab, n, total in hit:
+            lib.call('rscotr_swin_wattn_flush', tab.data_ptr(), n, total, _stream())
         self.wattn_entries = []
 
     def flush(self):
