@@ -4,7 +4,8 @@ import torch
 from torch.autograd import Function
 
 from .core import _WS, _Prof, _chk, _f32c, _off_path, _ptr, _sink, _stream, lib
-from .matmul import DEFER, RANGE_OUT, _linear_param_grad, colsum, gemm, gemm_batched, linear
+from .deferred import DEFER, WattnPart
+from .matmul import RANGE_OUT, _linear_param_grad, colsum, gemm, gemm_batched, linear
 from .ranges import RANGES
 from .state import STATE
 
@@ -51,7 +52,7 @@ class _SwinWindowAttn(Function):
             part = DEFER.reserve(nws, qkv.device)
             lib.call('rscotr_swin_wattn_bwd', qkv.data_ptr(), _ptr(qkv_b), table.data_ptr(), dout.data_ptr(),
                      dqkv.data_ptr(), 0, 0, B, H, W, C, heads, ws, shift, out.data_ptr(), part, nws, slot, _stream())
-            DEFER.wattn_entries.append((part, dt_ptr, db_ptr, heads, C, nws // (heads * 268 * 4)))
+            DEFER.wattn_entries.append(WattnPart(part, dt_ptr, db_ptr, heads, C, nws // (heads * 268 * 4)))
         else:
             with _Prof('swin_wattn_bwd', 4 * B * H * W * 8 * C):
                 lib.call('rscotr_swin_wattn_bwd', qkv.data_ptr(), _ptr(qkv_b), table.data_ptr(), dout.data_ptr(),

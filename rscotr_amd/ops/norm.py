@@ -3,7 +3,7 @@ import torch
 from torch.autograd import Function
 
 from .core import _WS, _Prof, _chk, _f32c, _ptr, _sink, _stream, lib
-from .matmul import DEFER
+from .deferred import DEFER, LnPart
 from .ranges import RANGES
 from .state import STATE
 
@@ -88,14 +88,14 @@ class _LayerNorm(Function):
             lib.call('rscotr_patch_merge_norm_bwd', g.data_ptr(), x2.data_ptr(), _ptr(w), stats[0].data_ptr(),
                      stats[1].data_ptr(), _ptr(dx), dw_ptr, db_ptr, *merge, ws_ptr, nws, 0 if defer else 1, slot, _stream())
             if defer:
-                DEFER.ln_entries.append((ws_ptr, dw_ptr, db_ptr, nws // (8 * C), C))
+                DEFER.ln_entries.append(LnPart(ws_ptr, dw_ptr, db_ptr, nws // (8 * C), C))
         elif defer:
             # the fold of the per-workgroup partial rows into dgamma / dbeta joins the end-of-pass flush (one launch for
             # all ~55 LayerNorms of a backward pass instead of one each)
             part = DEFER.reserve(nws, x2.device)
             lib.call('rscotr_layernorm_bwd_partials', g.data_ptr(), x2.data_ptr(), _ptr(w), stats[0].data_ptr(),
                      stats[1].data_ptr(), _ptr(dx), _ptr(r), M, C, part, nws, slot, _stream())
-            DEFER.ln_entries.append((part, dw_ptr, db_ptr, nws // (8 * C), C))
+            DEFER.ln_entries.append(LnPart(part, dw_ptr, db_ptr, nws // (8 * C), C))
         else:
             ws = _WS.get(nws, x2.device)
             with _Prof('layernorm_bwd', 12 * M * C):

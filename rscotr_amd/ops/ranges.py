@@ -40,7 +40,7 @@ class _Ranges:
         self.n = 0
         self.gen = 1
         self.route = {}
-        self.route2 = {}  # (... and on the kernel that takes a weight operand from pre-split planes: ops.matmul.HPLANES)
+        self.route2 = {}  # (... and on the kernel that takes a weight operand from pre-split planes: ops.planes.HPLANES)
         self.check = os.environ.get('RSCOTR_RANGES_CHECK') == '1'
         self.log = os.environ.get('RSCOTR_RANGES_STATS') == '1'
         self.sites = {}
@@ -171,7 +171,7 @@ class _Ranges:
         self.stats['measured'] += 1
         if self.log:
             import traceback
-            fr = [f for f in traceback.extract_stack(limit=12) if 'ranges.py' not in f.filename and f.name not in ('gemm', '_dw_ranges', '_try_defer_dw')]
+            fr = [f for f in traceback.extract_stack(limit=12) if 'ranges.py' not in f.filename and f.name not in ('gemm', '_try_defer_dw')]
             key = f'({rows} x {cols}) ' + ' < '.join(f'{f.name}:{f.lineno}' for f in reversed(fr[-4:]))
             self.sites[key] = self.sites.get(key, 0) + 1
         if ptr is None or ptr == t.data_ptr():
