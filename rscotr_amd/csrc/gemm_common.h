@@ -1,10 +1,9 @@
-// Shared pieces of the GEMM family (csrc/gemm.hip, csrc/gemm_pp.hip): the parameter block of a product, the fused
+// Shared pieces of the GEMM family (csrc/gemm*.hip, csrc/ranges.hip, csrc/ffn.hip): the parameter block of a product, the fused
 // epilogues, the XCD-aware tile order and the three-plane bf16 split.  See gemm.hip for the conventions.
 #pragma once
 #include "common.h"
 
 namespace rscotr {
-
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_RELU_GRAD = 3, ACT_GELU_GRAD = 4,
@@ -16,6 +15,7 @@ enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_RELU_GRAD = 3, ACT_GELU_GRA
        ACT_RELU_BITS = 5, ACT_RELU_GRAD_BITS = 6 };
 
 constexpr int GEMM_BK = 16;
+constexpr int X6_BK0 = 32;  // k per barrier pair of the one-stage loop (PIPE 0: the 128 x 128 kernels, the grouped launch's bodies).  Round 4 measured 32 at +0.2 ms per round on the six-term bf16 product (MFMA + conversion issue bound); on the fp16 product, which waits on memory for half of its wave life (profiles/r5_h3_64_pmc.txt), 32 is -0.6 ms: 33.73 against 34.32
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -54,7 +54,8 @@ struct GemmParams {
   // value ranges (round 5, the fp16 split product below): amax_a / amax_b -> the bit pattern of max |x| over (a superset
   // of) the operand, written by whoever produced the tensor (rscotr_amax_f32, an epilogue, the optimizer); both non-null
   // = the product may run on fp16 planes scaled by powers of two taken from them.  amax_out: the epilogue folds max |C|
-  // into this slot (atomicMax on the bit pattern: order-independent, hence deterministic).
+  // into this slot (amax_commit, common.h: one plain byte store per wavefront that marks the binade — idempotent, hence
+  // order-independent and deterministic).
   const unsigned* amax_a = nullptr;
   const unsigned* amax_b = nullptr;
   unsigned* amax_out = nullptr;
@@ -106,10 +107,7 @@ __device__ __forceinline__ float epilogue_one(const GemmParams& p, float v, int 
   return v;
 }
 
-
-// End of a kernel: the wavefront's max goes to p.amax_out with one atomicMax on the bit pattern (non-negative floats order
-// like unsigned integers; a maximum does not depend on the order of its operands: deterministic).  Every lane of the
-// wavefront must reach this call.
+// (end of a kernel: amax_commit, common.h — every lane of the wavefront must reach that call)
 
 // Four consecutive columns of one row (n % 4 == 0, p.vecC): every load is issued before the first store — the
 // element-wise form chains load -> store four times, and each wait also drains the store queued before it.
@@ -341,8 +339,8 @@ __device__ __forceinline__ unsigned pack_bf16(__bf16 a, __bf16 b) {
   return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
 }
 
-// ---- the fp16 split ("h3") of one value pair, shared by csrc/gemm.hip and csrc/ffn.hip (the comment block in front of
-// split_rows4_h in gemm.hip describes the arithmetic)
+// ---- the fp16 split ("h3") of one value pair, shared by the split-product kernels and csrc/ffn.hip (the comment block in front
+// of split_rows4_h in gemm_split_body.h describes the arithmetic)
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -358,7 +356,6 @@ __device__ __forceinline__ void split_pair_h(float a, float b, const H3Scale& k,
   out[1] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2_t));
 }
 
-// combine kernel for the split-K slabs of p (p.splits > 1): gemm.hip
+// combine kernel for the split-K slabs of p (p.splits > 1): gemm_reduce.hip
 void splitk_reduce_launch(const GemmParams& p, const float* workspace, hipStream_t s);
-
 }  // namespace rscotr

@@ -56,8 +56,9 @@ __global__ __launch_bounds__(256) void grad_sumsq_final_kernel(float* __restrict
   if (threadIdx.x == 0) sumsq[0] = part[0] + part[1] + part[2] + part[3];
 }
 
-// Value ranges of the parameters (round 5: the fp16 split product of csrc/gemm.hip scales a weight operand by a power of two
-// taken from max |w| of its tensor): seg_amax[segment] = bit pattern of max |w|.  The update kernel below leaves the maximum
+// Value ranges of the parameters (round 5: the fp16 split product of csrc/gemm_h3.hip scales a weight operand by a power of two
+// taken from max |w| of its tensor): seg_amax[segment] = the tensor's range word (the exponent map of common.h: the byte of the
+// binade of max |w| is set, written with plain stores).  The update kernel below leaves the maximum
 // of every wavefront's share of a chunk in chunk_amax[4 * chunk + wavefront] (plain stores), seg_amax_reduce_kernel — one
 // wavefront per segment, the segment's chunks found by bisection of the sorted chunk_seg — folds them into the words of the
 // segments that were stepped; the others keep theirs.  No atomics: the first cut folded each workgroup's maximum into the

@@ -1,5 +1,5 @@
 #!/bin/bash
-# register / scratch use of the kernels of one csrc file whose mangled name matches $2:  scripts/lab/kernel_regs.sh msda.hip 'tile_kernelILi32ELi4'
+# register / scratch use of the kernels of one csrc file whose mangled name matches $2:  scripts/lab/kernel_regs.sh gemm_h3.hip 'gemm_h3_kernelILi64ELi64E'
 cd "$(dirname "$0")/../.."
 SRC=${3:-rscotr_amd/csrc/$1}
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -I rscotr_amd/csrc -I include -w --cuda-device-only -S -x hip $SRC -o /tmp/kr.s || exit 1
