@@ -126,7 +126,7 @@ __device__ __forceinline__ void amax_commit(unsigned* slot, float amx) {
 }
 
 // Sampling location of mmcv MultiScaleDeformableAttention.forward from a reference point and a raw offset (ONE definition for the
-// stand-alone prologue kernel, csrc/attn.hip, and the forward kernel that does the prologue itself, csrc/msda.hip):
+// stand-alone prologue kernel, csrc/msda_prep.hip, and the forward kernel that does the prologue itself, csrc/msda_fwd.hip):
 //   2-d reference points: ref_xy + off / (W_l, H_l);   4-d: ref_xy + off / P * ref_wh * 0.5
 __device__ __forceinline__ float2 msda_location(const float* __restrict__ r, float2 o, const float* __restrict__ norm, int l, int P,
                                                 int refdim) {

@@ -9,7 +9,8 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(params=['tiled', 'sorted', 'scatter'], autouse=True)
 def bwd_strategy(request):
-    """Both grad_value strategies of rscotr_msda_bwd run every test (include/rscotr.h)."""
+    """All three grad_value strategies of rscotr_msda_bwd run every test (include/rscotr.h; what each request is served
+    by is decided in one place, plan_msda_bwd of csrc/msda.hip)."""
     from rscotr_amd import ops
     with ops.STATE.override(msda_bwd=request.param):
         yield request.param
@@ -30,19 +31,28 @@ def _inputs(B, shapes, Nq, H, D, P, seed, spread=0.15, dev='cpu'):
     return value, ss, lsi, loc, attn
 
 
-def _run_pair(value, ss, lsi, loc, attn, cuda):
-    from rscotr_amd import ops
-    # oracle (CPU)
+def _grad_out(shape):
+    return torch.randn(shape, generator=torch.Generator().manual_seed(7))
+
+
+def _run_oracle(value, ss, lsi, loc, attn):
     v0, l0, a0 = (t.clone().requires_grad_(True) for t in (value, loc, attn))
     out0 = O.msda_sample(v0, ss, lsi, l0, a0)
-    go = torch.randn(out0.shape, generator=torch.Generator().manual_seed(7))
-    out0.backward(go)
-    # HIP
+    out0.backward(_grad_out(out0.shape))
+    return out0.detach(), v0.grad, l0.grad, a0.grad
+
+
+def _run_hip(value, ss, lsi, loc, attn, cuda):
+    from rscotr_amd import ops
     v1, l1, a1 = (t.clone().to(cuda).requires_grad_(True) for t in (value, loc, attn))
     out1 = ops.msda(v1, ss.to(cuda), lsi.to(cuda), l1, a1)
-    out1.backward(go.to(cuda))
+    out1.backward(_grad_out(out1.shape).to(cuda))
     torch.cuda.synchronize()
-    return (out0, v0.grad, l0.grad, a0.grad), (out1.cpu(), v1.grad.cpu(), l1.grad.cpu(), a1.grad.cpu())
+    return out1.detach().cpu(), v1.grad.cpu(), l1.grad.cpu(), a1.grad.cpu()
+
+
+def _run_pair(value, ss, lsi, loc, attn, cuda):
+    return _run_oracle(value, ss, lsi, loc, attn), _run_hip(value, ss, lsi, loc, attn, cuda)
 
 
 def _close(a, b, rtol=1e-3, atol=None):
@@ -57,6 +67,36 @@ def test_msda_small(cuda, B, Nq, H, D, P):
     shapes = [(12, 9), (6, 5), (3, 3), (2, 1)]
     ref, got = _run_pair(*_inputs(B, shapes, Nq, H, D, P, seed=B * 100 + Nq), cuda)
     for r, g in zip(ref, got):
+        _close(r, g)
+
+
+# Routes of the backward planner (csrc/msda.hip: plan_msda_bwd) and of the forward launcher that the model shapes never take.
+# (B, levels, Nq, H, D, P); the oracle runs once per case and serves the three strategies.
+_NINE = [(5, 4), (4, 4), (4, 3), (3, 3), (3, 2), (2, 2), (2, 1), (1, 2), (1, 1)]
+ROUTE_CASES = {
+    # nine levels: msda_tiles_build refuses more than 8, so a tiled request is served by the sorted strategy
+    'tiled_served_by_sorted': (1, _NINE, 37, 2, 32, 1),
+    # seventeen levels: neither workspace query offers anything, every setting scatters with atomics into a grad_value
+    # that ops/deform.py must then have zeroed
+    'scatter_under_every_setting': (1, (_NINE + _NINE)[:17], 37, 2, 32, 2),
+    # D = 16, L P = 32: the forward records of a tile are 64 KB (per-lane path), the sample kernel's LDS 96 KB + 64 B
+    'per_lane_forward_and_lds_above_64k': (1, [(12, 9), (6, 5), (3, 3), (2, 1)], 65, 2, 16, 8),
+}
+_ROUTE_REF = {}
+
+
+@pytest.mark.parametrize('case', sorted(ROUTE_CASES))
+def test_msda_routes_the_models_never_take(cuda, case):
+    B, shapes, Nq, H, D, P = ROUTE_CASES[case]
+    inputs = _inputs(B, shapes, Nq, H, D, P, seed=len(case))
+    if case not in _ROUTE_REF:
+        _ROUTE_REF[case] = _run_oracle(*inputs)
+    # what the caching allocator hands to the next torch.empty_like(value): anything but zeros
+    junk = torch.full(inputs[0].shape, 1.0e4, device=cuda)
+    del junk
+    got = _run_hip(*inputs, cuda)
+    for r, g in zip(_ROUTE_REF[case], got):
+        assert torch.isfinite(g).all()
         _close(r, g)
 
 
@@ -197,7 +237,7 @@ def test_sine_embed4_matches_reference_formula(cuda):
 def test_msda_large_pyramids(cuda, bwd_strategy, shapes, Nq):
     """The pyramids of BASELINE configs[3] / configs[4] at their full token counts, and one whose host-side bin bound
     (2 Nk + 2 L + 2) exceeds the LDS histogram of the sorted strategy (the kernels decide on the device from the level
-    shapes whether that path runs or stands down for the atomic scatter: csrc/msda.hip, MSDA_LDS_WORDS): every strategy
+    shapes whether that path runs or stands down for the atomic scatter: csrc/msda_bwd_sorted.hip, MSDA_LDS_WORDS): every strategy
     against the ORACLE (seg_head/pixel_decoder.py:134-146, bbox_head/transformer.py:211-221 reach the op at these shapes)."""
     L = len(shapes)
     value, ss, lsi, loc, attn = _inputs(1, shapes, Nq, 8, 32, 4, seed=11, spread=0.05)
