@@ -732,6 +732,33 @@ int rscotr_img_frames_u8(const uint8_t* src, const int64_t* meta, const int32_t*
 int rscotr_randaug_u8(const uint8_t* in, uint8_t* out, const int32_t* meta, const int32_t* warp, const int16_t* wtab,
                       uint32_t* stats, int need_stats, int B, int H, int W, void* stream);
 
+/* Segmentation evaluation on the device (csrc/seg_eval.hip): the inference tail of MTL.simple_test_seg and mmseg's
+ * pre_eval areas (additive entries: the ABI revision is unchanged).
+ *
+ * rscotr_seg_predict_u8: out[b, y, x] = argmax over c of the logits resampled as whole_inference_seg does it, one launch,
+ * no up-sampled tensor.  logit: device fp32 (B, C, h, w), contiguous.  (H, W): the padded canvas the logits are first
+ * resampled to.  rescale != 0: that map is cropped to (hs, ws) (img_shape of meta 0) and resampled to (Ho, Wo) (ori_shape);
+ * out is uint8 (B, Ho, Wo).  rescale == 0: hs, ws, Ho, Wo are ignored and out is uint8 (B, H, W).  One set of sizes per launch
+ * (the reference reads img_meta[0] for the whole batch).  Every output pixel's logit is the composition of the two bilinear
+ * resamplings of ATen with align_corners = False in fp32, stage 1 per tap, then stage 2: source index
+ * max((dst + 0.5) * (in / out) - 0.5, 0), upper tap min(i0 + 1, in - 1) with `in` the cropped extent in stage 2 — plain,
+ * non-antialiased bilinear also where ori_shape is smaller than img_shape.  No softmax (monotone).  The arg-max takes the first
+ * index on ties, a NaN logit wins and the first NaN wins among several (torch.argmax).  flip: 0 none, 1 horizontal, 2
+ * vertical, applied to the output coordinates (out[y][x] = map[y][Wo - 1 - x] for 1).  RSCOTR_E_SHAPE: C > 255, a non-positive
+ * size, a crop larger than the canvas, B > 65535; RSCOTR_E_ARG: a null pointer, another flip value.
+ *
+ * rscotr_seg_areas_u8: mmseg intersect_and_union of a batch.  pred, gt: device uint8 (B, Hp, Wp), gt the RAW label maps.
+ * reduce_zero_label != 0: label 0 becomes 255, every other label shifts down by one (255 stays).  Pixels whose label equals
+ * ignore_index are dropped.  out: device int64 (B, 4, C), ZEROED BY THE CALLER and added to: row 0 area_intersect[c] = kept
+ * pixels with pred == label == c, row 1 area_union = row 2 + row 3 - row 0, row 2 area_pred_label[c] = kept pixels with
+ * pred == c, row 3 area_label[c] = kept pixels with label == c; a value >= C falls out of its own histogram only (torch.histc
+ * in mmseg).  Per-workgroup LDS histograms, then 64-bit integer adds: exact in any order, so the result is bit-reproducible.
+ * RSCOTR_E_SHAPE: a non-positive size, C > 256, B > 65535, Hp * Wp >= 2^31. */
+int rscotr_seg_predict_u8(const float* logit, uint8_t* out, int B, int C, int h, int w, int H, int W, int rescale, int hs,
+                          int ws, int Ho, int Wo, int flip, void* stream);
+int rscotr_seg_areas_u8(const uint8_t* pred, const uint8_t* gt, int64_t* out, int B, int Hp, int Wp, int C, int ignore_index,
+                        int reduce_zero_label, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

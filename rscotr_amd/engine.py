@@ -8,6 +8,9 @@ its task (what the reference borrows from mmcls / mmdet / mmseg `apis.single_gpu
 to the dataset's own classes, and returns `{dataset_name: results}`; `multi_gpu_test` runs the same loops on every
 rank's shard and gathers the shards in the interleaved order of mmcv's `collect_results_gpu`.
 
+With `kwargs_dict=dict(seg=dict(pre_eval=True))` (the reference configs' mode) the seg loop keeps every image's class areas
+instead of its label map: prediction and areas are computed on the device and reach the host in one transfer per dataset.
+
 `MultiDatasetsEvalHook` evaluates every `interval` iterations (or epochs) from `start` on, calls each dataset's
 `evaluate(results, logger=..., **eval_kwargs[task])`, publishes `'{dataset}.{metric}'` values to the runner's log
 buffer, and — with `save_best` (a key, a list of keys or a {key: weight} dict) — keeps the checkpoint whose WEIGHTED
@@ -19,7 +22,9 @@ from collections import OrderedDict
 import torch
 
 
-def _loop(model, loader, **kwargs):
+def _loop(model, loader, *, per_batch=None, **kwargs):
+    """`model(return_loss=False, **data)` per batch in eval mode; the results concatenated, or, with `per_batch`, what
+    `per_batch(result)` makes of each batch's result, one entry per batch."""
     results = []
     was_training = model.training
     model.eval()
@@ -27,7 +32,10 @@ def _loop(model, loader, **kwargs):
         for data in loader:
             with torch.no_grad():
                 result = model(return_loss=False, **dict(data, **kwargs))
-            results.extend(result if isinstance(result, (list, tuple)) else [result])
+            if per_batch is not None:
+                results.append(per_batch(result))
+            else:
+                results.extend(result if isinstance(result, (list, tuple)) else [result])
     finally:
         model.train(was_training)
     return results
@@ -45,8 +53,28 @@ def _test_det(model, loader, show=False, out_dir=None, show_score_thr=0.3, **kwa
 
 def _test_seg(model, loader, show=False, out_dir=None, efficient_test=False, opacity=0.5, pre_eval=False,
               format_only=False, format_args=None, **kwargs):
-    """mmseg.apis.single_gpu_test (plain mode): per-image label maps at the original size."""
-    return _loop(model, loader, **kwargs)
+    """mmseg.apis.single_gpu_test: per-image label maps at the original size, or, with `pre_eval`, per-image 4-tuples
+    (area_intersect, area_union, area_pred_label, area_label) of int64 CPU vectors — mmseg's pre-eval results.  In that mode
+    the label maps never leave the device (`model(..., on_device=True)`), every batch is reduced to its (b, 4, C) areas by
+    `loader.dataset.pre_eval(preds, indices)` as soon as it is made, and ONE transfer after the loop brings all of them to
+    the host: no sync per batch, no label map kept."""
+    if not pre_eval:
+        return _loop(model, loader, **kwargs)
+    # dataset indices of a batch: the loader's batch sampler when it has one, else running positions (DeviceLoader in
+    # test mode walks the dataset in order)
+    sampler = getattr(loader, 'batch_sampler', None)
+    batches = iter(sampler) if sampler is not None else None
+    seen = [0]
+
+    def reduce(preds):
+        indices = list(next(batches)) if batches is not None else list(range(seen[0], seen[0] + len(preds)))
+        seen[0] += len(preds)
+        return loader.dataset.pre_eval(preds, indices)
+    areas = _loop(model, loader, per_batch=reduce, on_device=True, **kwargs)
+    if not areas:
+        return []
+    host = torch.cat([torch.as_tensor(a) for a in areas], 0).cpu()  # (N, 4, C): the loop's only device-to-host copy
+    return [tuple(a.unbind(0)) for a in host.unbind(0)]
 
 
 single_gpu_single_dataset_test = dict(cv=_loop, cls=_test_cls, det=_test_det, seg=_test_seg)
@@ -127,7 +155,7 @@ class MultiDatasetsEvalHook:
     init_value_map = {'greater': -float('inf'), 'less': float('inf')}
 
     def __init__(self, dataloaders, start=None, interval=1, by_epoch=True, save_best=None, test_fn=None,
-                 greater_keys=None, less_keys=None, out_dir=None, file_client_args=None, **eval_kwargs):
+                 greater_keys=None, less_keys=None, out_dir=None, file_client_args=None, test_kwargs=None, **eval_kwargs):
         if not isinstance(dataloaders, dict):
             raise TypeError(f'dataloaders must be a dict of loaders, but got {type(dataloaders)}')
         if interval <= 0:
@@ -144,6 +172,8 @@ class MultiDatasetsEvalHook:
             save_best = {key: 1 for key in save_best}
         self.save_best = save_best
         self.eval_kwargs = eval_kwargs
+        # {task: kwargs} handed to the test function as `kwargs_dict` (e.g. dict(seg=dict(pre_eval=True))); None = its defaults
+        self.test_kwargs = test_kwargs
         self.initial_flag = True
         self.test_fn = single_gpu_test if test_fn is None else test_fn
         self.greater_keys, self.less_keys = greater_keys, less_keys
@@ -188,7 +218,10 @@ class MultiDatasetsEvalHook:
 
     # ---- evaluation.py:118-148 -----------------------------------------------------------------------------------
     def _do_evaluate(self, runner):
-        results_dict = self.test_fn(runner.model, self.dataloaders)
+        if self.test_kwargs is None:
+            results_dict = self.test_fn(runner.model, self.dataloaders)
+        else:
+            results_dict = self.test_fn(runner.model, self.dataloaders, kwargs_dict=self.test_kwargs)
         runner.log_buffer_output['eval_iter_num'] = {name: len(dl) for name, dl in self.dataloaders.items()}
         key_score = self.evaluate(runner, results_dict)
         # the key_score may be `None` (or 0) so it needs to skip the action to save the best checkpoint

@@ -6,7 +6,8 @@ dataset classes, restated from their published definitions:
 * `seg_metrics(...)`        mmseg `CustomDataset.evaluate(metric=['mIoU', 'mFscore', 'mDice'])` / `eval_metrics`: one confusion
                             matrix accumulated ON THE DEVICE (`torch.bincount` of gt * C + pred over every image), then aAcc, per-class
                             IoU / Acc / Dice / F-score / precision / recall and their nan-means, as fractions rounded like mmseg's
-                            (`round(x * 100, 2) / 100`).
+                            (`round(x * 100, 2) / 100`).  `seg_metrics_from_areas(...)` gives the same values from the per-class
+                            total areas of mmseg's pre_eval mode.
 * `coco_bbox_map(...)`      mmdet `CocoDataset.evaluate(metric='bbox', iou_thrs=..., classwise=...)` = pycocotools `COCOeval`
                             (bbox, no crowd): per (image, class) greedy matching in score order at every IoU threshold with the
                             area-range ignore rules, 101-point interpolated precision, AP = mean over thresholds x recall points x
@@ -63,13 +64,23 @@ def confusion_matrix(preds, gts, num_classes, ignore_index=255, reduce_zero_labe
 
 def seg_metrics(cm, class_names, metrics=('mIoU',), beta=1, nan_to_num=None):
     """mmseg `total_area_to_metrics` + the key layout of `CustomDataset.evaluate` from a confusion matrix (rows = label)."""
+    cm = cm.double().cpu()
+    return _area_metrics(cm.diag(), cm.sum(0), cm.sum(1), class_names, metrics, beta, nan_to_num)
+
+
+def seg_metrics_from_areas(area_intersect, area_pred_label, area_label, class_names, metrics=('mIoU',), beta=1,
+                           nan_to_num=None):
+    """The same metrics from the per-class total areas of mmseg's pre_eval mode (sums over the images of
+    `intersect_and_union`: pixels with pred == label == c, with pred == c, with label == c; the union follows)."""
+    vec = lambda a: torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).double().cpu().reshape(-1)
+    return _area_metrics(vec(area_intersect), vec(area_pred_label), vec(area_label), class_names, metrics, beta, nan_to_num)
+
+
+def _area_metrics(inter, pred, label, class_names, metrics, beta, nan_to_num):
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
     allowed = ('mIoU', 'mDice', 'mFscore')
     if not set(metrics).issubset(allowed):
         raise KeyError(f'metrics {metrics} is not supported')
-    cm = cm.double().cpu()
-    inter = cm.diag()
-    label, pred = cm.sum(1), cm.sum(0)
     union = label + pred - inter
     ret = OrderedDict(aAcc=(inter.sum() / label.sum()).reshape(1))
     for m in metrics:

@@ -250,7 +250,27 @@ class MTL(nn.Module):
             output = output.flip(dims=(3,)) if direction == 'horizontal' else output.flip(dims=(2,))
         return output
 
-    def simple_test_seg(self, img, img_meta, rescale=True):
+    def predict_seg_device(self, img, img_meta, rescale):
+        """inference_seg + argmax as ONE launch on the head's logits (ops.seg_predict): uint8 (B, Ho, Wo) on the device,
+        no up-sampled tensor, no softmax (monotone), no host sync."""
+        assert self.test_cfg['seg']['mode'] in ['whole'] and not self.seg_head.align_corners
+        ori_shape = img_meta[0]['ori_shape']
+        assert all(_['ori_shape'] == ori_shape for _ in img_meta)
+        neck_feature, backbone_feature = self.extract_feat(img)
+        seg_logit = self.seg_head.forward_test(neck_feature, backbone_feature, img_meta, self.shared_encoder)
+        flip = None
+        if img_meta[0].get('flip', False):
+            flip = img_meta[0]['flip_direction']
+            assert flip in ['horizontal', 'vertical']
+        if not rescale:
+            return ops.seg_predict(seg_logit, img.shape[2:], flip=flip)
+        return ops.seg_predict(seg_logit, img.shape[2:], crop_hw=img_meta[0]['img_shape'][:2], out_hw=ori_shape[:2], flip=flip)
+
+    def simple_test_seg(self, img, img_meta, rescale=True, on_device=False):
+        """-> per-image label maps: int64 NumPy maps on the host, or, with `on_device`, uint8 device tensors (the pre_eval
+        loop of rscotr_amd.engine reduces them to class areas without leaving the device)."""
+        if on_device:
+            return list(self.predict_seg_device(img, img_meta, rescale).unbind(0))
         seg_pred = self.inference_seg(img, img_meta, rescale).argmax(dim=1)
         return list(seg_pred.cpu().numpy())
 

@@ -1,0 +1,45 @@
+"""Segmentation evaluation on the device: the inference tail of MTL.simple_test_seg (resample, flip, arg-max) and mmseg's
+pre_eval areas (intersect_and_union), one launch each (csrc/seg_eval.hip).  Neither op synchronises with the host."""
+import torch
+
+from .core import _chk, _f32c, _stream, lib
+
+_FLIP = {None: 0, False: 0, 'horizontal': 1, 'vertical': 2}
+
+
+def seg_predict(logit, canvas_hw, crop_hw=None, out_hw=None, flip=None):
+    """logit (B, C, h, w) -> uint8 label maps (B, Ho, Wo): arg-max over the channels of the logits resampled to the canvas
+    (bilinear, align_corners=False) and, when `out_hw` is given (rescale), cropped to `crop_hw` (default: the canvas) and
+    resampled to `out_hw`; without it the maps have the canvas size.  flip: None | 'horizontal' | 'vertical', applied to
+    the finished map.  See include/rscotr.h, rscotr_seg_predict_u8."""
+    if flip not in _FLIP:
+        raise ValueError(f"flip must be None, 'horizontal' or 'vertical', got {flip!r}")
+    logit = _f32c(logit.detach())
+    _chk(logit)
+    B, C, h, w = logit.shape
+    H, W = (int(v) for v in canvas_hw)
+    rescale = out_hw is not None
+    if crop_hw is not None and not rescale:
+        raise ValueError('crop_hw needs out_hw (the crop belongs to the rescale stage)')
+    hs, ws = (H, W) if crop_hw is None else (int(v) for v in crop_hw)
+    Ho, Wo = (int(v) for v in out_hw) if rescale else (H, W)
+    out = torch.empty((B, max(Ho, 0), max(Wo, 0)), dtype=torch.uint8, device=logit.device)
+    lib.call('rscotr_seg_predict_u8', logit.data_ptr(), out.data_ptr(), B, C, h, w, H, W, int(rescale), hs, ws, Ho, Wo,
+             _FLIP[flip], _stream())
+    return out
+
+
+def seg_areas(pred, gt, num_classes, ignore_index=255, reduce_zero_label=False):
+    """pred, gt uint8 (B, Hp, Wp) (gt: raw label maps) -> int64 (B, 4, C): area_intersect, area_union, area_pred_label,
+    area_label per image and class (mmseg intersect_and_union).  See include/rscotr.h, rscotr_seg_areas_u8."""
+    if pred.dtype != torch.uint8 or gt.dtype != torch.uint8:
+        raise TypeError('seg_areas takes uint8 prediction and label maps')
+    if pred.dim() != 3 or pred.shape != gt.shape:
+        raise ValueError(f'prediction {tuple(pred.shape)} and label maps {tuple(gt.shape)} must both be (B, Hp, Wp)')
+    pred, gt = pred.contiguous(), gt.contiguous()
+    _chk(pred, gt)
+    B, Hp, Wp = pred.shape
+    out = torch.zeros((B, 4, max(int(num_classes), 0)), dtype=torch.int64, device=pred.device)
+    lib.call('rscotr_seg_areas_u8', pred.data_ptr(), gt.data_ptr(), out.data_ptr(), B, Hp, Wp, int(num_classes),
+             int(ignore_index), int(bool(reduce_zero_label)), _stream())
+    return out

@@ -1130,22 +1130,60 @@ class TileSegDataset:
             seg = np.asarray(im).astype(np.uint8)
         return dict(img=_imread_bgr(ip), gt_semantic_seg=seg, filename=ip)
 
-    def evaluate(self, results, metric='mIoU', logger=None, gt_seg_maps=None, device=None, **kwargs):
-        """mmseg CustomDataset.evaluate: `results` = per-image label maps at the original size (dataset order) -> aAcc, mIoU / mAcc,
-        mFscore / mPrecision / mRecall, mDice and the per-class values, as fractions.  The confusion matrix is accumulated on the
-        device (rscotr_amd/metrics.py); `pre_eval` / `classwise` of the reference's config are accepted and change nothing here
-        (per-class values are always returned)."""
+    def _label_map(self, i):
         from PIL import Image
-        from .metrics import confusion_matrix, seg_metrics
-        assert len(results) == len(self.items), 'one label map per image'
+        with Image.open(self.items[i][1]) as im:
+            return np.asarray(im).astype(np.uint8)
+
+    def pre_eval(self, preds, indices, device=None):
+        """mmseg CustomDataset.pre_eval for one batch: `preds` = the label maps (uint8 device tensors, or NumPy maps) of the
+        images `indices` -> int64 (len(preds), 4, C) on the device: area_intersect, area_union, area_pred_label, area_label
+        per image (ops.seg_areas).  The raw label tiles are read and uploaded as uint8; nothing comes back to the host.
+        These are mmseg's areas: a kept pixel whose prediction is >= C (a head with more channels than the dataset has
+        classes) still counts in area_label, whereas the confusion matrix of the label-map route drops that pixel — see
+        `evaluate`."""
+        indices = [int(i) for i in indices]
+        assert len(preds) == len(indices), 'one index per prediction'
+        if device is None:
+            device = preds[0].device if torch.is_tensor(preds[0]) and preds[0].is_cuda else 'cuda'
+        dev = torch.device(device)
+
+        def u8(p):
+            if not torch.is_tensor(p):
+                p = torch.from_numpy(np.ascontiguousarray(p))
+            if p.dtype != torch.uint8:  # (host maps are int64: a label that does not fit a byte must not wrap into a class)
+                if p.numel() and (int(p.min()) < 0 or int(p.max()) > 255):
+                    raise ValueError('pre_eval takes label maps with values in 0 .. 255')
+                p = p.to(torch.uint8)
+            return p.to(dev)
+        pred = torch.stack([u8(p) for p in preds])
+        gt = torch.from_numpy(np.stack([self._label_map(i) for i in indices])).to(dev)
+        return ops.seg_areas(pred, gt, len(self.CLASSES), ignore_index=self.ignore_index,
+                             reduce_zero_label=self.reduce_zero_label)
+
+    def evaluate(self, results, metric='mIoU', logger=None, gt_seg_maps=None, device=None, **kwargs):
+        """mmseg CustomDataset.evaluate -> aAcc, mIoU / mAcc, mFscore / mPrecision / mRecall, mDice and the per-class values, as
+        fractions.  `results` (dataset order) are either per-image label maps at the original size (arrays or tensors: the
+        confusion matrix is accumulated on the device, rscotr_amd/metrics.py) or the per-image 4-tuples (area_intersect,
+        area_union, area_pred_label, area_label) of the pre_eval test loop (`engine._test_seg(pre_eval=True)`), which are summed
+        over the images and need no label map here.  The `pre_eval` / `classwise` keys of the reference's config are accepted:
+        the kind of `results` decides the route, and per-class values are always returned.  The two routes agree exactly
+        while every prediction is a class of the dataset (< C).  They differ for a pixel predicted >= C: mmseg's areas keep it
+        in area_label (it lowers aAcc, Acc and Recall, as in the reference's pre_eval mode), the confusion matrix drops it
+        from every count."""
+        from .metrics import confusion_matrix, seg_metrics, seg_metrics_from_areas
+        assert len(results) == len(self.items), 'one result per image'
+        if len(results) and isinstance(results[0], (tuple, list)) and len(results[0]) == 4:
+            total = sum(torch.stack([torch.as_tensor(a).reshape(-1).cpu().long() for a in r]) for r in results)
+            return seg_metrics_from_areas(total[0], total[2], total[3], self.CLASSES, metrics=metric)
 
         def gts():
             if gt_seg_maps is not None:
                 yield from gt_seg_maps
                 return
-            for _, ap in self.items:
-                with Image.open(ap) as im:
-                    yield np.asarray(im).astype(np.uint8)
+            for i in range(len(self.items)):
+                yield self._label_map(i)
+        results = [r.cpu().numpy() if torch.is_tensor(r) else r for r in results]
         cm = confusion_matrix(results, gts(), len(self.CLASSES), ignore_index=self.ignore_index,
                               reduce_zero_label=self.reduce_zero_label, device=device)
         return seg_metrics(cm, self.CLASSES, metrics=metric)
