@@ -759,6 +759,44 @@ int rscotr_seg_predict_u8(const float* logit, uint8_t* out, int B, int C, int h,
 int rscotr_seg_areas_u8(const uint8_t* pred, const uint8_t* gt, int64_t* out, int B, int Hp, int Wp, int C, int ignore_index,
                         int reduce_zero_label, void* stream);
 
+/* Detection evaluation on the device (csrc/det_eval.hip): the inference tail of DINOHead._get_bboxes_single and
+ * COCOeval.evaluateImg as rscotr_amd/metrics.py `_evaluate_img` states it (additive entries: no argument list changed, so the ABI
+ * revision is unchanged; a library without them fails to bind by name).  Neither entry synchronises with the host.
+ *
+ * rscotr_det_decode_f32: one launch, one workgroup per image.  cls: device fp32 (B, Q, C) last-layer class logits; box: device
+ * fp32 (B, Q, 4) normalised cxcywh, 16-byte aligned; meta: device fp32 (B, 6) = img_h, img_w and the four scale-factor
+ * entries (w, h, w, h).  score = sigmoid(logit) in fp32; the K largest scores over the flat (query, class) index are selected
+ * exactly, TIES GO TO THE LOWER FLAT INDEX, a NaN score ranks above every number; rows come in torch.topk(sorted=True) order.
+ * dets: device fp32 (B, K, 5) = x1, y1, x2, y2, score; labels: device int64 (B, K) = idx % C, the box that of query idx / C
+ * through the fp32 operation sequence of the torch chain, each product, sum and quotient rounded on its own:
+ * (cx -/+ 0.5 * w) * img_w, (cy -/+ 0.5 * h) * img_h, clamp to [0, img_w] / [0, img_h] (a NaN stays), and, with rescale != 0, an
+ * IEEE divide by the scale-factor entry of the column.  The box columns are bit-equal to that chain in fp32 on the CPU; the
+ * score differs from torch's by the rounding of exp only.  RSCOTR_E_SHAPE: Q * C > 36864, K > min(Q * C, 1024), a non-positive
+ * size (the caller keeps the torch chain there); RSCOTR_E_ALIGN: box.  LDS: 4 * Q * C + 8 KB, as rscotr_det_proposals.
+ *
+ * rscotr_det_match: one launch, one workgroup per (image, class).  dets (B, K, 5) fp32 and labels (B, K) int64 as above, rows
+ * in descending score order per image; n_det: device int32 (B), rows k >= n_det[b] do not exist.  Ground truths of the batch
+ * concatenated: gt_boxes device fp32 (G, 4) xyxy, 16-byte aligned, gt_labels device int64 (G), gt_offsets device int64 (B + 1)
+ * (image b owns rows gt_offsets[b] .. gt_offsets[b + 1]).  area_ranges: device fp64 (A, 2); iou_thrs: device fp64 (T).
+ * flags: device int32 (B, K, A), every word written: for area range a, bit t = the detection is matched at threshold t, bit
+ * 16 + t = it is ignored at threshold t, 0x80000000 alone = it is dropped (beyond the first max_det detections of its class in
+ * the image, k >= n_det[b], or a label outside [0, C); all A words of such a row).  With T == 16 bit 31 is also "ignored at
+ * threshold 15", and the word stays unambiguous: an evaluated detection ignored at 15 is either matched there (bit 15 too) or
+ * unmatched with its own area outside the range, and then at threshold 0 it is matched (bit 0) or ignored (bit 16).
+ * npig: device int32 (B, C, A), the ground truths of the class whose area lies in the range.  Rules, to the comparison, of `_evaluate_img`: IoU and areas in fp64 from the fp32 boxes in the
+ * order of `_iou_xyxy`, inter / ((ad + ag) - inter), no contraction; per threshold the detections in score order each take the
+ * unmatched ground truth of IoU not below min(t, 1 - 1e-10) that the host's walk ends on: a regular one before an ignored
+ * one (area outside the range), then the largest IoU, then the LATER of equal ones; an unmatched detection whose own area is
+ * outside the range is ignored.  Integer accumulation only: identical from run to run.
+ * CAPS: at most 1024 ground truths per (image, class) (the caller checks this on the host, where it knows the counts; the
+ * kernel evaluates the first 1024 and stays in bounds); RSCOTR_E_SHAPE: K > 1024, T > 16, min(max_det, K) * A > 8192, a
+ * non-positive size.  max_det itself is not capped.  LDS: 20 KB + 4 * min(max_det, K) * A bytes. */
+int rscotr_det_decode_f32(const float* cls, const float* box, const float* meta, float* dets, int64_t* labels, int B, int Q,
+                          int C, int K, int rescale, void* stream);
+int rscotr_det_match(const float* dets, const int64_t* labels, const int32_t* n_det, const float* gt_boxes,
+                     const int64_t* gt_labels, const int64_t* gt_offsets, const double* area_ranges, const double* iou_thrs,
+                     int32_t* flags, int32_t* npig, int B, int K, int64_t G, int C, int A, int T, int max_det, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -850,8 +850,10 @@ class DINOHead(nn.Module):
         return torch.stack(outputs_classes), torch.stack(outputs_coords), topk_score, topk_anchor
 
     # ---- inference: dino_head.py:79-82 + mmdet_detr_head/detr_head.py:590-682 ------------------------
-    def simple_test(self, feats, img_metas, shared_encoder=None, rescale=False):
+    def simple_test(self, feats, img_metas, shared_encoder=None, rescale=False, on_device=False):
         outs = self(shared_encoder, feats, img_metas)
+        if on_device:
+            return self.get_bboxes_device(*outs, img_metas, rescale=rescale)
         return self.get_bboxes(*outs, img_metas, rescale=rescale)
 
     def get_bboxes(self, all_cls_scores, all_bbox_preds, enc_topk_scores, enc_topk_anchors, img_metas, rescale=False):
@@ -859,6 +861,25 @@ class DINOHead(nn.Module):
         cls_scores, bbox_preds = all_cls_scores[-1], all_bbox_preds[-1]
         return [self._get_bboxes_single(cls_scores[i], bbox_preds[i], m['img_shape'], m['scale_factor'], rescale)
                 for i, m in enumerate(img_metas)]
+
+    def get_bboxes_device(self, all_cls_scores, all_bbox_preds, enc_topk_scores, enc_topk_anchors, img_metas, rescale=False):
+        """`get_bboxes` for the whole batch in one launch (ops.det_decode) -> per image (dets (K, 5), labels (K,)) device
+        tensors, no host sync.  One small upload carries img_shape and scale_factor of every image.  Ties between equal
+        scores go to the lower (query, class) index, which torch.topk leaves unspecified.  Outside the kernel's limits
+        (Q * C > 36864 or max_per_img > min(Q * C, 1024)) the torch chain of `_get_bboxes_single` runs instead."""
+        cls_scores, bbox_preds = all_cls_scores[-1], all_bbox_preds[-1]
+        B, Q, C = cls_scores.shape
+        K = (self.test_cfg or {}).get('max_per_img', self.num_query)
+        if not ops.det_decode_fits(Q, C, K):
+            return self.get_bboxes(all_cls_scores, all_bbox_preds, enc_topk_scores, enc_topk_anchors, img_metas, rescale=rescale)
+        rows = []
+        for m in img_metas:
+            sf = m['scale_factor']
+            sf = [float(v) for v in sf] if hasattr(sf, '__len__') else [float(sf)] * 4
+            rows.append([float(m['img_shape'][0]), float(m['img_shape'][1]), *sf])
+        meta = torch.tensor(rows, dtype=torch.float32).to(cls_scores.device)
+        dets, labels = ops.det_decode(cls_scores, bbox_preds, meta, K, rescale)
+        return list(zip(dets.unbind(0), labels.unbind(0)))
 
     def _get_bboxes_single(self, cls_score, bbox_pred, img_shape, scale_factor, rescale=False):
         """sigmoid -> top-k over (query, class) -> boxes in pixels, clipped, optionally un-scaled."""

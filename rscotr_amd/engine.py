@@ -10,6 +10,8 @@ rank's shard and gathers the shards in the interleaved order of mmcv's `collect_
 
 With `kwargs_dict=dict(seg=dict(pre_eval=True))` (the reference configs' mode) the seg loop keeps every image's class areas
 instead of its label map: prediction and areas are computed on the device and reach the host in one transfer per dataset.
+With `kwargs_dict=dict(det=dict(on_device=True))` the det loop does the same for detection: boxes are decoded and matched
+against the ground truths on the device, and the per-image match flags reach the host in one transfer per dataset.
 
 `MultiDatasetsEvalHook` evaluates every `interval` iterations (or epochs) from `start` on, calls each dataset's
 `evaluate(results, logger=..., **eval_kwargs[task])`, publishes `'{dataset}.{metric}'` values to the runner's log
@@ -46,9 +48,49 @@ def _test_cls(model, loader, show=False, out_dir=None, **kwargs):
     return _loop(model, loader, **kwargs)
 
 
-def _test_det(model, loader, show=False, out_dir=None, show_score_thr=0.3, **kwargs):
-    """mmdet.apis.single_gpu_test: per-image lists of per-class (k, 5) arrays, boxes in original-image coordinates."""
-    return _loop(model, loader, rescale=True, **kwargs)
+def _batch_indices(loader):
+    """-> f(n): the dataset indices of the next batch of n results: the loader's batch sampler when it has one, else running
+    positions (DeviceLoader in test mode walks the dataset in order)."""
+    sampler = getattr(loader, 'batch_sampler', None)
+    batches = iter(sampler) if sampler is not None else None
+    seen = [0]
+
+    def take(n):
+        indices = list(next(batches)) if batches is not None else list(range(seen[0], seen[0] + n))
+        seen[0] += n
+        return indices
+    return take
+
+
+def _test_det(model, loader, show=False, out_dir=None, show_score_thr=0.3, on_device=False, iou_thrs=None, max_det=100,
+              **kwargs):
+    """mmdet.apis.single_gpu_test: per-image lists of per-class (k, 5) arrays, boxes in original-image coordinates.  With
+    `on_device` the detections never leave the device during the loop: every batch is decoded by one launch
+    (`model(..., on_device=True)`) and matched against its ground truths by another
+    (`loader.dataset.pre_eval(dets, labels, indices, iou_thrs=..., max_det=...)`: the thresholds and max_det that `evaluate`
+    will be called with), and ONE device-to-host copy after the loop brings everything over: -> per image a picklable tuple
+    (dets (K, 5), labels (K,), flags (K, A), npig (C, A)) of CPU tensors, which `CocoDetDataset.evaluate` accumulates.  A
+    dataset whose ground truths exceed the matching kernel's cap hands back the per-class lists instead."""
+    if not on_device:
+        return _loop(model, loader, rescale=True, **kwargs)
+    take = _batch_indices(loader)
+
+    def reduce(result):
+        return loader.dataset.pre_eval([d for d, _ in result], [l for _, l in result], take(len(result)), iou_thrs=iou_thrs,
+                                       max_det=max_det)
+    per_image = [r for batch in _loop(model, loader, per_batch=reduce, rescale=True, on_device=True, **kwargs) for r in batch]
+    if not per_image or not isinstance(per_image[0], tuple):
+        return per_image
+    # one byte buffer for the four kinds (int64 first: every segment starts at a multiple of its element size)
+    kinds = [torch.stack([r[i] for r in per_image]).contiguous() for i in (1, 0, 2, 3)]
+    host = torch.cat([k.view(torch.uint8).reshape(-1) for k in kinds]).cpu()  # the loop's only device-to-host copy
+    parts, at = [], 0
+    for k in kinds:
+        n = k.numel() * k.element_size()
+        parts.append(host[at:at + n].view(k.dtype).reshape(k.shape).clone())
+        at += n
+    labels, dets, flags, npig = parts
+    return [tuple(t) for t in zip(dets.unbind(0), labels.unbind(0), flags.unbind(0), npig.unbind(0))]
 
 
 def _test_seg(model, loader, show=False, out_dir=None, efficient_test=False, opacity=0.5, pre_eval=False,
@@ -60,16 +102,10 @@ def _test_seg(model, loader, show=False, out_dir=None, efficient_test=False, opa
     the host: no sync per batch, no label map kept."""
     if not pre_eval:
         return _loop(model, loader, **kwargs)
-    # dataset indices of a batch: the loader's batch sampler when it has one, else running positions (DeviceLoader in
-    # test mode walks the dataset in order)
-    sampler = getattr(loader, 'batch_sampler', None)
-    batches = iter(sampler) if sampler is not None else None
-    seen = [0]
+    take = _batch_indices(loader)
 
     def reduce(preds):
-        indices = list(next(batches)) if batches is not None else list(range(seen[0], seen[0] + len(preds)))
-        seen[0] += len(preds)
-        return loader.dataset.pre_eval(preds, indices)
+        return loader.dataset.pre_eval(preds, take(len(preds)))
     areas = _loop(model, loader, per_batch=reduce, on_device=True, **kwargs)
     if not areas:
         return []

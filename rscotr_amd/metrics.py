@@ -198,6 +198,11 @@ def coco_bbox_map(results, gt_boxes, gt_labels, class_names, iou_thrs=None, max_
                         q[ri] = pr[pi]
                 precision[ti, :, k, a] = q
 
+    return _coco_summarize(precision, iou_thrs, class_names, classwise)
+
+
+def _coco_summarize(precision, iou_thrs, class_names, classwise):
+    """COCOeval.summarize + mmdet's key layout from precision (T, R, K, areas), -1 where undefined."""
     def summarize(iou=None, area='all'):
         s = precision[:, :, :, list(_AREA).index(area)]
         if iou is not None:
@@ -215,3 +220,65 @@ def coco_bbox_map(results, gt_boxes, gt_labels, class_names, iou_thrs=None, max_
         out[f'bbox_{key}'] = float(f'{v:.3f}')
     out['bbox_mAP_copypaste'] = ' '.join(f'{v:.3f}' for v in stats)
     return out
+
+
+DET_DROPPED = -(1 << 31)  # flag word of a detection that takes no part (int32 0x80000000)
+
+
+def coco_iou_thrs(iou_thrs=None):
+    """The thresholds `coco_bbox_map` evaluates: COCO's ten by default."""
+    return np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True) if iou_thrs is None else np.asarray(iou_thrs, dtype=np.float64)
+
+
+def coco_area_ranges():
+    """(A, 2) float64: COCO's all / small / medium / large."""
+    return np.asarray(list(_AREA.values()), dtype=np.float64)
+
+
+def coco_accumulate(results, class_names, iou_thrs=None, classwise=False):
+    """COCOeval.accumulate + summarize over pre-matched detections: `results` = per image, in dataset order, a tuple
+    (dets (K, 5) [x1, y1, x2, y2, score] in descending score order, labels (K,), flags (K, A) int32, npig (C, A)) as
+    `ops.det_match` / `CocoDetDataset.pre_eval` make them for the SAME `iou_thrs` (flags: bit t = matched at threshold t,
+    bit 16 + t = ignored at t, DET_DROPPED = not evaluated; npig: non-ignored ground truths).  -> exactly the dict of
+    `coco_bbox_map` on the same detections, vectorised: per class one stable sort by descending score, per area range
+    cumulative tp / fp, the precision envelope and the 101-point recall sampling."""
+    iou_thrs = coco_iou_thrs(iou_thrs)
+    rec_thrs = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+    K, T, R, A = len(class_names), len(iou_thrs), len(rec_thrs), len(_AREA)
+    arr = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    if len(results):
+        score = np.concatenate([arr(r[0]).reshape(-1, 5)[:, 4] for r in results]).astype(np.float64)
+        label = np.concatenate([arr(r[1]).reshape(-1) for r in results])
+        flags = np.concatenate([arr(r[2]).reshape(-1, A) for r in results]).astype(np.int64) & 0xffffffff
+        npig = np.sum([arr(r[3]).reshape(K, A).astype(np.int64) for r in results], axis=0)
+    else:
+        score, label, flags, npig = np.zeros(0), np.zeros(0, np.int64), np.zeros((0, A), np.int64), np.zeros((K, A), np.int64)
+    # a dropped row has DET_DROPPED in all A words; no evaluated row has that word, at T == 16 either (bit 31 = ignored at
+    # threshold 15 then comes with bit 15, bit 0 or bit 16: include/rscotr.h), so range 0 decides
+    live = flags[:, 0] != (1 << 31) if len(flags) else np.zeros(0, bool)
+    tbit = np.arange(T)
+    precision = -np.ones((T, R, K, A))
+    for k in range(K):
+        if not npig[k].any():
+            continue
+        rows = np.nonzero(live & (label == k))[0]  # dataset order, score order within an image
+        rows = rows[np.argsort(-score[rows], kind='mergesort')]
+        for a in range(A):
+            if npig[k, a] == 0:
+                continue
+            f = flags[rows, a]
+            m = ((f[None, :] >> tbit[:, None]) & 1).astype(bool)         # (T, n)
+            ig = ((f[None, :] >> (16 + tbit[:, None])) & 1).astype(bool)
+            tp = np.cumsum(m & ~ig, axis=1).astype(np.float64)
+            fp = np.cumsum(~m & ~ig, axis=1).astype(np.float64)
+            n = tp.shape[1]
+            if n == 0:
+                precision[:, :, k, a] = 0.0
+                continue
+            pr = tp / (fp + tp + np.spacing(1))
+            pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]  # precision envelope
+            rc = tp / npig[k, a]
+            for ti in range(T):
+                inds = np.searchsorted(rc[ti], rec_thrs, side='left')
+                precision[ti, :, k, a] = np.where(inds < n, pr[ti, np.minimum(inds, n - 1)], 0.0)
+    return _coco_summarize(precision, iou_thrs, class_names, classwise)

@@ -220,10 +220,15 @@ class MTL(nn.Module):
         neck_feature, backbone_feature = self.extract_feat(img, with_neck=getattr(self.cls_head, 'needs_neck', True))
         return self.cls_head.simple_test(neck_feature, backbone_feature, shared_encoder=self.shared_encoder, **kwargs)
 
-    def simple_test_det(self, img, img_metas, rescale=False):
+    def simple_test_det(self, img, img_metas, rescale=False, on_device=False):
+        """-> per image the per-class list of (k, 5) arrays of mmdet's bbox2result, or, with `on_device`, the tuple
+        (dets (K, 5), labels (K,)) of device tensors decoded by one launch for the batch (the pre_eval loop of
+        rscotr_amd.engine matches them against the ground truths without leaving the device)."""
         for m in img_metas:
             m['batch_input_shape'] = tuple(img.size()[-2:])
         feat = self.extract_feat(img)[0]
+        if on_device:
+            return self.bbox_head.simple_test(feat, img_metas, rescale=rescale, shared_encoder=self.shared_encoder, on_device=True)
         results_list = self.bbox_head.simple_test(feat, img_metas, rescale=rescale, shared_encoder=self.shared_encoder)
         return [bbox2result(b, l, self.bbox_head.num_classes) for b, l in results_list]
 

@@ -18,13 +18,14 @@ CPU tensor, or a non-zero return code raises.
     losses     box utilities, match_cost_batched, lsap_*, focal / box loss sums, upsample_ce
     distutil   packed scalar all-reduces
     seg_eval   seg_predict (resample + flip + arg-max of the seg logits), seg_areas (mmseg pre_eval areas)
+    det_eval   det_decode (sigmoid + top-k + box decoding of a batch), det_match (COCOeval's per-image matching)
 
 Callers use `from rscotr_amd import ops; ops.linear(...)`: every public (and test-visible) name of the submodules is
 re-exported here (submodule names differ from every op name: `ops.gemm` and `ops.msda` are the functions)."""
-from . import attention, core, deferred, deform, distutil, fused, glue, losses, matmul, norm, planes, ranges, seg_eval, state
+from . import attention, core, deferred, deform, det_eval, distutil, fused, glue, losses, matmul, norm, planes, ranges, seg_eval, state
 from .state import STATE
 
-for _m in (core, ranges, deferred, planes, fused, matmul, norm, deform, attention, glue, losses, distutil, seg_eval):
+for _m in (core, ranges, deferred, planes, fused, matmul, norm, deform, attention, glue, losses, distutil, seg_eval, det_eval):
     for _k, _v in vars(_m).items():
         if not _k.startswith('__') and _k not in ('STATE',):
             globals().setdefault(_k, _v)

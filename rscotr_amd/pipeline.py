@@ -1092,17 +1092,71 @@ class CocoDetDataset:
         path, boxes, labels = self.items[i]
         return dict(img=_imread_bgr(path), gt_bboxes=boxes, gt_labels=labels, filename=path)
 
+    def device_eval_ok(self):
+        """Whether `ops.det_match` takes this dataset: no (image, class) holds more ground truths than its cap (counted once,
+        on the host)."""
+        ok = getattr(self, '_device_eval_ok', None)
+        if ok is None:
+            most = max((int(np.bincount(it[2]).max()) for it in self.items if len(it[2])), default=0)
+            ok = self._device_eval_ok = most <= ops.DET_MATCH_MAX_GT
+        return ok
+
+    def pre_eval(self, dets, labels, indices, iou_thrs=None, max_det=100, device=None):
+        """COCOeval.evaluateImg for one batch on the device.  dets: per image (K, 5) device tensors [x1, y1, x2, y2, score] in
+        original-image coordinates and descending score order (or one (B, K, 5) tensor), labels: (K,) int64 each, `indices`:
+        their positions in the dataset.  The ground truths of those images are uploaded and `ops.det_match` runs with COCO's
+        area ranges, `iou_thrs` (default: COCO's ten) and `max_det`.  -> per image a tuple (dets, labels, flags (K, A) int32,
+        npig (C, A) int32) of device tensors, the kind `evaluate` accumulates with `metrics.coco_accumulate`; nothing comes
+        back to the host.  A dataset with more than `ops.DET_MATCH_MAX_GT` ground truths of one class in one image takes the
+        host route instead: -> per image the per-class list of (k, 5) arrays of `mtl.bbox2result`."""
+        from .metrics import coco_area_ranges, coco_iou_thrs
+        indices = [int(i) for i in indices]
+        assert len(dets) == len(labels) == len(indices), 'one index per image'
+        C = len(self.CLASSES)
+        if not indices:
+            return []
+        if not self.device_eval_ok():
+            from .mtl import bbox2result
+            return [bbox2result(d, l, C) for d, l in zip(dets, labels)]
+        dets = dets if torch.is_tensor(dets) else torch.stack(list(dets))
+        labels = labels if torch.is_tensor(labels) else torch.stack(list(labels))
+        dev = torch.device(device) if device is not None else dets.device
+        dets, labels = dets.to(dev, torch.float32), labels.to(dev, torch.int64)
+        B, K = labels.shape
+        thrs = coco_iou_thrs(iou_thrs)
+        self._pre_eval_cfg = (tuple(float(t) for t in thrs), int(max_det))
+        gb = [self.items[i][1].reshape(-1, 4) for i in indices]
+        gl = [self.items[i][2].reshape(-1) for i in indices]
+        off = np.concatenate([[0], np.cumsum([len(g) for g in gl])]).astype(np.int64)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        flags, npig = ops.det_match(dets, labels, torch.full((B,), K, dtype=torch.int32, device=dev),
+                                    up(np.concatenate(gb).astype(np.float32)), up(np.concatenate(gl).astype(np.int64)), up(off),
+                                    up(coco_area_ranges()), up(thrs), C, int(max_det))
+        return [tuple(t) for t in zip(dets.unbind(0), labels.unbind(0), flags.unbind(0), npig.unbind(0))]
+
     def evaluate(self, results, metric='bbox', logger=None, jsonfile_prefix=None, classwise=False, proposal_nums=(100, 300, 1000),
                  iou_thrs=None, metric_items=None, **kwargs):
-        """mmdet CocoDataset.evaluate(metric='bbox'): `results` = per image a list (per class) of (k, 5) arrays in original-image
-        coordinates -> bbox_mAP / _50 / _75 / _s / _m / _l (COCOeval semantics, rscotr_amd/metrics.py)."""
-        from .metrics import coco_bbox_map
+        """mmdet CocoDataset.evaluate(metric='bbox') -> bbox_mAP / _50 / _75 / _s / _m / _l (COCOeval semantics,
+        rscotr_amd/metrics.py).  `results` (dataset order) are either per image a LIST (per class) of (k, 5) arrays in
+        original-image coordinates, matched and accumulated on the host (`coco_bbox_map`), or per image a TUPLE (dets, labels,
+        flags, npig) of the pre_eval test loop (`engine._test_det(on_device=True)`), matched on the device and only accumulated
+        here (`coco_accumulate`): the kind of `results` decides the route, and both give the same dict.  The tuples must have
+        been matched with this call's `iou_thrs` and `max_det = proposal_nums[0]`: that is the caller's contract.  The check below only catches the common slip (it
+        compares with the last `pre_eval` of THIS object; tuples unpickled from another process are taken on trust)."""
+        from .metrics import coco_accumulate, coco_bbox_map, coco_iou_thrs
         metrics = [metric] if isinstance(metric, str) else list(metric)
         if metrics != ['bbox']:
             raise KeyError(f'metric {metrics} is not supported (bbox only)')
         assert len(results) == len(self.items), 'one result per image'
-        out = coco_bbox_map(results, [it[1] for it in self.items], [it[2] for it in self.items], self.CLASSES, iou_thrs=iou_thrs,
-                            max_det=proposal_nums[0], classwise=classwise)
+        if len(results) and isinstance(results[0], tuple) and len(results[0]) == 4:
+            cfg = getattr(self, '_pre_eval_cfg', None)
+            if cfg is not None and cfg != (tuple(float(t) for t in coco_iou_thrs(iou_thrs)), int(proposal_nums[0])):
+                raise ValueError(f'results were pre-evaluated with (iou_thrs, max_det) = {cfg}, evaluate() asks for '
+                                 f'{(iou_thrs, proposal_nums[0])}')
+            out = coco_accumulate(results, self.CLASSES, iou_thrs=iou_thrs, classwise=classwise)
+        else:
+            out = coco_bbox_map(results, [it[1] for it in self.items], [it[2] for it in self.items], self.CLASSES,
+                                iou_thrs=iou_thrs, max_det=proposal_nums[0], classwise=classwise)
         if metric_items is not None:
             keep = {f'bbox_{m}' for m in metric_items}
             out = type(out)((k, v) for k, v in out.items() if k in keep or k == 'bbox_mAP_copypaste' or k.startswith('bbox_AP.'))
