@@ -29,7 +29,9 @@ extern "C" {
 
 /* ABI revision: bumped whenever an exported entry changes its argument list (round 5 inserted amax_out / nbytes before
  * `stream` in the LayerNorm, window-attention, MSDA backward, pack4, splitk_flush and grouped-dW entries = revision 6;
- * round 6 = 7; 11 added the resampling input entries rscotr_img_aug_u8 / rscotr_seg_label_aug_u8).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
+ * round 6 = 7; 11 added the resampling input entries rscotr_img_aug_u8 / rscotr_seg_label_aug_u8; the
+ * evaluation entries since — seg_predict / seg_areas, det_decode / det_match, seg_predict_tta — are additive and change no
+ * argument list, so they keep 11: a library without them fails to bind by name).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
  * its first call (rscotr_amd/_lib.py does) — a stale .so would take a stream handle for a pointer. */
 #define RSCOTR_ABI_VERSION 11
 int rscotr_version(void);
@@ -758,6 +760,24 @@ int rscotr_seg_predict_u8(const float* logit, uint8_t* out, int B, int C, int h,
                           int ws, int Ho, int Wo, int flip, void* stream);
 int rscotr_seg_areas_u8(const uint8_t* pred, const uint8_t* gt, int64_t* out, int B, int Hp, int Wp, int C, int ignore_index,
                         int reduce_zero_label, void* stream);
+
+/* Multi-scale / flip test-time augmentation of the segmentation tail (csrc/seg_eval.hip; mmseg EncoderDecoder.aug_test with
+ * mode 'whole'; an additive entry: the ABI revision is unchanged).
+ *
+ * rscotr_seg_predict_tta_u8: out[b, y, x] = argmax over c of (sum over the V views of softmax_c(view v's logits resampled to
+ * (Ho, Wo) and un-flipped)) / V, one launch, no up-sampled tensor.  views: a HOST array of V rows of 8 int64, read before the
+ * call returns and passed to the kernel by value (no upload, no device-side table): {device address of that view's logits
+ * (B, C, h, w) fp32 contiguous, h, w, H, W, hs, ws, flip} with (H, W) the view's padded canvas, (hs, ws) its img_shape crop
+ * and flip 0 none / 1 horizontal / 2 vertical, acting on the finished (Ho, Wo) map as in rscotr_seg_predict_u8.  B, C and the
+ * output size (Ho, Wo) (ori_shape) are common to the views.  Per view every output pixel takes the composed two-stage bilinear
+ * value of rscotr_seg_predict_u8 (rescale != 0) for every channel, then softmax over the channels in fp32 as torch does it
+ * (subtract the channel maximum, expf, divide by the sum), and adds the probabilities to per-pixel accumulators that live in
+ * LDS (the first view stores); after the last view acc[c] / V (IEEE division) goes through torch.argmax's tie and NaN rules.
+ * A NaN logit makes every channel of the pixels in its footprint NaN (softmax), so those pixels get label 0.  out: device uint8
+ * (B, Ho, Wo).  The views are accumulated in row order, so the result is bit-reproducible.  RSCOTR_E_SHAPE: V outside 1 .. 16,
+ * C > 255, a non-positive size, a crop larger than its canvas, C * h * w >= 2^31, B > 65535; RSCOTR_E_ARG: a null pointer or
+ * logit address, another flip value.  Every check precedes the first HIP call. */
+int rscotr_seg_predict_tta_u8(const int64_t* views, uint8_t* out, int V, int B, int C, int Ho, int Wo, void* stream);
 
 /* Detection evaluation on the device (csrc/det_eval.hip): the inference tail of DINOHead._get_bboxes_single and
  * COCOeval.evaluateImg as rscotr_amd/metrics.py `_evaluate_img` states it (additive entries: no argument list changed, so the ABI

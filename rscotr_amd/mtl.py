@@ -206,6 +206,8 @@ class MTL(nn.Module):
             task = task[0]
         if isinstance(img, list):
             if len(img) != 1:
+                if task == 'seg' and isinstance(img_metas[0], list) and len(img_metas) == len(img):
+                    return self.aug_test_seg(img, img_metas, *args, **kwargs)
                 raise NotImplementedError('The current implementation does not support TTA ')
             img = img[0]
         if isinstance(img_metas[0], list):
@@ -279,6 +281,38 @@ class MTL(nn.Module):
         seg_pred = self.inference_seg(img, img_meta, rescale).argmax(dim=1)
         return list(seg_pred.cpu().numpy())
 
+    def aug_test_seg(self, imgs, img_metas, rescale=True, on_device=False):
+        """mmseg EncoderDecoder.aug_test (multi-scale / flip testing): `imgs` = V views of one batch, `img_metas` = their V meta
+        lists.  Per view inference_seg (resample to the canvas, crop, resample to ori_shape, softmax, un-flip); the mean over the
+        views, arg-max.  -> per-image int64 NumPy maps, or, with `on_device`, uint8 device tensors: the V forward passes keep
+        only their head logits and ONE launch (ops.seg_predict_tta) does the whole tail, no up-sampled tensor, no host sync."""
+        assert rescale  # (aug_test rescales to the original shape)
+        assert len(imgs) == len(img_metas) and len(imgs) >= 1
+        if not on_device:
+            seg_prob = self.inference_seg(imgs[0], img_metas[0], rescale)
+            for img, meta in zip(imgs[1:], img_metas[1:]):
+                ops.RANGES.begin(img.device)  # (every view is a forward pass of its own)
+                seg_prob += self.inference_seg(img, meta, rescale)
+            seg_prob /= len(imgs)
+            return list(seg_prob.argmax(dim=1).cpu().numpy())
+        assert self.test_cfg['seg']['mode'] in ['whole'] and not self.seg_head.align_corners
+        ori_shape = img_metas[0][0]['ori_shape']
+        assert all(_['ori_shape'] == ori_shape for meta in img_metas for _ in meta)
+        logits, canvases, crops, flips = [], [], [], []
+        for v, (img, meta) in enumerate(zip(imgs, img_metas)):
+            if v:
+                ops.RANGES.begin(img.device)
+            neck_feature, backbone_feature = self.extract_feat(img)
+            logits.append(self.seg_head.forward_test(neck_feature, backbone_feature, meta, self.shared_encoder))
+            flip = None
+            if meta[0].get('flip', False):
+                flip = meta[0]['flip_direction']
+                assert flip in ['horizontal', 'vertical']
+            canvases.append(tuple(img.shape[2:]))
+            crops.append(tuple(meta[0]['img_shape'][:2]))
+            flips.append(flip)
+        return list(ops.seg_predict_tta(logits, canvases, crops, ori_shape[:2], flips).unbind(0))
+
     # -------------------------------------------------------------------------------------
     def load_state_dict(self, *args, **kwargs):
         ops.WPLANES.bump()  # parameters change in place: the pre-split weight planes are stale
@@ -288,7 +322,7 @@ class MTL(nn.Module):
 
     def forward(self, task, img, img_metas, return_loss=True, dataset_name=None, **kwargs):
         ops.WPLANES.begin(task)  # (the weight-plane sets this task uses are refreshed together)
-        ops.RANGES.begin(img.device)  # (value-range slots of the GEMM operands: one generation per iteration)
+        ops.RANGES.begin((img[0] if isinstance(img, (list, tuple)) else img).device)  # (value-range slots of the GEMM operands: one generation per iteration)
         if return_loss:
             return self.forward_train(task=task, img=img, img_metas=img_metas, **kwargs)
         with torch.no_grad():

@@ -17,7 +17,8 @@ CPU tensor, or a non-zero return code raises.
     glue       level_embed_add, fan_out, cdn_queries, sine_embed4, neck im2col, layout helpers, cls pooling / loss
     losses     box utilities, match_cost_batched, lsap_*, focal / box loss sums, upsample_ce
     distutil   packed scalar all-reduces
-    seg_eval   seg_predict (resample + flip + arg-max of the seg logits), seg_areas (mmseg pre_eval areas)
+    seg_eval   seg_predict (resample + flip + arg-max of the seg logits), seg_predict_tta (the same over V views: softmax, mean,
+               arg-max), seg_areas (mmseg pre_eval areas)
     det_eval   det_decode (sigmoid + top-k + box decoding of a batch), det_match (COCOeval's per-image matching)
 
 Callers use `from rscotr_amd import ops; ops.linear(...)`: every public (and test-visible) name of the submodules is

@@ -1,5 +1,7 @@
-"""Segmentation evaluation on the device: the inference tail of MTL.simple_test_seg (resample, flip, arg-max) and mmseg's
-pre_eval areas (intersect_and_union), one launch each (csrc/seg_eval.hip).  Neither op synchronises with the host."""
+"""Segmentation evaluation on the device: the inference tail of MTL.simple_test_seg (resample, flip, arg-max), that of
+MTL.aug_test_seg (the same over V views: softmax, mean, arg-max) and mmseg's pre_eval areas (intersect_and_union), one launch
+each (csrc/seg_eval.hip).  No op synchronises with the host."""
+import numpy as np
 import torch
 
 from .core import _chk, _f32c, _stream, lib
@@ -26,6 +28,38 @@ def seg_predict(logit, canvas_hw, crop_hw=None, out_hw=None, flip=None):
     out = torch.empty((B, max(Ho, 0), max(Wo, 0)), dtype=torch.uint8, device=logit.device)
     lib.call('rscotr_seg_predict_u8', logit.data_ptr(), out.data_ptr(), B, C, h, w, H, W, int(rescale), hs, ws, Ho, Wo,
              _FLIP[flip], _stream())
+    return out
+
+
+def seg_predict_tta(logits, canvases, crops, out_hw, flips):
+    """Multi-scale / flip test-time augmentation (mmseg aug_test, mode 'whole') as ONE launch.  logits: V tensors
+    (B, C, h_v, w_v) with the same B and C on one device; canvases[v]: the padded input size (H, W) of view v; crops[v]: its
+    img_shape (hs, ws), or None for the canvas; flips[v]: None | 'horizontal' | 'vertical'; out_hw: the common ori_shape
+    (Ho, Wo).  -> uint8 label maps (B, Ho, Wo): arg-max over the channels of the mean over the views of softmax(view resampled
+    to the canvas, cropped, resampled to out_hw, un-flipped).  See include/rscotr.h, rscotr_seg_predict_tta_u8."""
+    V = len(logits)
+    if not (len(canvases) == len(crops) == len(flips) == V):
+        raise ValueError(f'one canvas, crop and flip per view: {V} logits, {len(canvases)} canvases, {len(crops)} crops, '
+                         f'{len(flips)} flips')
+    for f in flips:
+        if f not in _FLIP:
+            raise ValueError(f"flip must be None, 'horizontal' or 'vertical', got {f!r}")
+    for t in logits:
+        if t.dim() != 4 or t.shape[:2] != logits[0].shape[:2] or t.device != logits[0].device:
+            raise ValueError(f'every view is (B, C, h, w) with the same B and C on one device: {[tuple(t.shape) for t in logits]}')
+    if V == 0:
+        raise ValueError('seg_predict_tta takes at least one view')
+    Ho, Wo = (int(v) for v in out_hw)
+    held = [_f32c(t.detach()) for t in logits]  # (alive until the launch is enqueued)
+    _chk(*held)
+    B, C = held[0].shape[:2]
+    rows = np.zeros((V, 8), dtype=np.int64)
+    for v, (t, canvas, crop, flip) in enumerate(zip(held, canvases, crops, flips)):
+        H, W = (int(a) for a in canvas)
+        hs, ws = (H, W) if crop is None else (int(a) for a in crop)
+        rows[v] = [t.data_ptr(), t.shape[2], t.shape[3], H, W, hs, ws, _FLIP[flip]]
+    out = torch.empty((B, max(Ho, 0), max(Wo, 0)), dtype=torch.uint8, device=held[0].device)
+    lib.call('rscotr_seg_predict_tta_u8', rows.ctypes.data, out.data_ptr(), V, B, C, Ho, Wo, _stream())
     return out
 
 

@@ -289,7 +289,7 @@ class DeviceCollate:
     def __init__(self, task, device, img_norm_cfg=None, flip_prob=0.5, size_divisor=None, crop_size=None,
                  cat_max_ratio=1.0, reduce_zero_label=False, seg_pad_val=255, ignore_index=255, resize=None,
                  random_resized_crop=None, photometric=None, random_erasing=None, resize_backend='cv2',
-                 rand_augment=None):
+                 rand_augment=None, labels=True):
         """Optional stages (None = off; any of them on routes the batch through `rscotr_img_aug_u8`):
         resize: mmseg / mmdet Resize, dict(img_scale=(long, short), ratio_range=None | (lo, hi), keep_ratio=True), or
                 mmcls Resize, dict(size=(h, w)) (a fixed size);
@@ -299,7 +299,8 @@ class DeviceCollate:
         resize_backend: 'cv2' (bilinear) | 'pillow' (bicubic), the image resample of resize / random_resized_crop;
         rand_augment: mmcls RandAugment (task 'cls' only), True (RAND_AUGMENT, the reference's settings) or dict(policies,
                 num_policies, magnitude_level, total_level=30, magnitude_std=0., hparams); it routes the batch through
-                `rscotr_img_frames_u8` -> `rscotr_randaug_u8` per slot -> `rscotr_img_aug_u8`."""
+                `rscotr_img_frames_u8` -> `rscotr_randaug_u8` per slot -> `rscotr_img_aug_u8`;
+        labels: False = a seg batch without `gt_semantic_seg` (test time: the label maps are neither staged nor resampled)."""
         assert task in ('cls', 'det', 'seg')
         self.task, self.device = task, torch.device(device)
         cfg = dict(IMG_NORM if img_norm_cfg is None else img_norm_cfg)
@@ -327,6 +328,7 @@ class DeviceCollate:
         self.augmented = any(x is not None for x in (self.resize, self.rrc, self.photometric, self.erasing,
                                                      self.rand_augment))
         self.skipped = []  # transforms build_collate was told to skip
+        self.labels = bool(labels)
         self._stage_done = None  # event after the last upload out of the staging buffer (augmented path)
 
     # ---- host-side random decisions (the draws of mmcv / mmseg / mmdet RandomFlip and mmseg RandomCrop) ----------
@@ -687,7 +689,8 @@ class DeviceCollate:
     def _call_augmented(self, samples, rng):
         B = len(samples)
         imgs = [s['img'] for s in samples]
-        segs = [s.get('gt_semantic_seg') for s in samples]
+        with_labels = self.task == 'seg' and self.labels
+        segs = [s.get('gt_semantic_seg') if self.labels else None for s in samples]
         ds = []
         for img, seg in zip(imgs, segs):
             assert img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3, 'decoded HWC uint8 images expected'
@@ -715,7 +718,7 @@ class DeviceCollate:
             yt, ky = add(_AXIS[mode](sh, rh, sy, y0, ch))
             geo.append((mode, xt, kx, yt, ky))
         lgeo = []
-        if self.task == 'seg':
+        if with_labels:
             for seg, d in zip(segs, ds):
                 (sx, sy, sw, sh), (rw, rh), (x0, y0, cw, ch) = d['src'], d['rsz'], d['win']
                 assert seg is not None and seg.shape[:2] == imgs[len(lgeo)].shape[:2]
@@ -732,7 +735,7 @@ class DeviceCollate:
             if d['pm'] is not None:
                 params[b, :3] = d['pm'][1:4]
         nimg = len(imgs)
-        lsegs = [np.ascontiguousarray(sg) for sg in segs] if self.task == 'seg' else []
+        lsegs = [np.ascontiguousarray(sg) for sg in segs] if with_labels else []
         # layout of the one upload: images | label maps | erasing patches | tables | params | meta | label meta
         meta = np.zeros((max(B, 1), AUG_META), np.int64)
         lmeta = np.zeros((max(B, 1), AUG_META), np.int64)
@@ -792,7 +795,7 @@ class DeviceCollate:
                 hlabels.append(np.ascontiguousarray(hl))
             batch['gt_bboxes'], batch['gt_labels'] = boxes, labels
             batch['gt_bboxes_host'], batch['gt_labels_host'] = hboxes, hlabels
-        else:
+        elif with_labels:
             lab = torch.empty((B, 1, Hout, Wout), dtype=torch.int64, device=self.device)
             lib.call('rscotr_seg_label_aug_u8', ptr, p_lmeta, p_tab, lab.data_ptr(), B, Hout, Wout,
                      int(self.reduce_zero_label), int(self.seg_pad_val), ops._stream())
@@ -815,7 +818,7 @@ class DeviceCollate:
             return self._call_augmented(samples, rng)
         B = len(samples)
         imgs = [s['img'] for s in samples]
-        segs = [s.get('gt_semantic_seg') for s in samples]
+        segs = [s.get('gt_semantic_seg') if self.labels else None for s in samples]
         wins, flips = [], []
         for img, seg in zip(imgs, segs):
             assert img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3, 'decoded HWC uint8 images expected'
@@ -856,7 +859,7 @@ class DeviceCollate:
                 hlabels.append(np.ascontiguousarray(hl))
             batch['gt_bboxes'], batch['gt_labels'] = boxes, labels
             batch['gt_bboxes_host'], batch['gt_labels_host'] = hboxes, hlabels  # (for the det head's packed batch layout)
-        else:
+        elif self.labels:
             lbuf, loffs = self._stage_bytes(segs)
             lmeta = meta.clone()
             lmeta[:, 0] = torch.tensor(loffs, dtype=torch.int64)
@@ -921,6 +924,80 @@ def eval_collate_for(task, device, **kw):
     return DeviceCollate(task, device, **dict(cfg, **kw))
 
 
+SEG_TTA_MAX_VIEWS = 16  # rscotr_seg_predict_tta_u8 takes its view table in the kernel arguments: at most 16 rows
+
+
+def plan_tta_views(img_scale=None, img_ratios=None, flip=False, flip_direction='horizontal', img_hw=None):
+    """The views of mmseg's MultiScaleFlipAug, in its order -> [(scale (w, h), flip, direction | None)].
+    An `img_scale` tuple with `img_ratios` gives (int(W * r), int(H * r)) per ratio; `img_scale=None` with `img_ratios` the same
+    from the image's own size `img_hw` = (h, w); a list of scales (or one tuple without ratios) is used as is.  Scales are the
+    outermost loop, then flip in [False, True] when `flip`, then the directions (mmseg walks the directions for the unflipped
+    view too, so several directions repeat it)."""
+    ratios = None if img_ratios is None else (list(img_ratios) if isinstance(img_ratios, (list, tuple)) else [img_ratios])
+    if img_scale is None:
+        if not ratios:
+            raise ValueError('MultiScaleFlipAug: img_scale=None needs img_ratios')
+        if img_hw is None:
+            raise ValueError('MultiScaleFlipAug(img_scale=None): the views depend on the image size (img_hw)')
+        h, w = int(img_hw[0]), int(img_hw[1])
+        scales = [(int(w * r), int(h * r)) for r in ratios]
+    elif isinstance(img_scale, tuple) and ratios:
+        assert len(img_scale) == 2
+        scales = [(int(img_scale[0] * r), int(img_scale[1] * r)) for r in ratios]
+    else:
+        scales = [tuple(sc) for sc in img_scale] if isinstance(img_scale, list) else [tuple(img_scale)]
+    directions = list(flip_direction) if isinstance(flip_direction, (list, tuple)) else [flip_direction]
+    return [(sc, f, d if f else None) for sc in scales for f in ([False, True] if flip else [False]) for d in directions]
+
+
+class SegTTACollate:
+    """Test-time augmentation collate of the seg task: one DeviceCollate pass (device resize + normalise, forced flip) per view
+    of a MultiScaleFlipAug -> dict(img=[V tensors], img_metas=[V lists]), what `MTL.forward_test` hands to `aug_test_seg`.
+    `tta`: the MultiScaleFlipAug arguments of `plan_tta_views`; `resize`: the keyword arguments of its Resize other than the
+    scale; every other keyword goes to the per-view DeviceCollate, which is built without the label stage (a test batch is
+    `img` and `img_metas` only).  All images of a batch must have one shape (the views of
+    a batch share their sizes and their ori_shape)."""
+
+    def __init__(self, device, tta, resize=None, **kw):
+        self.task, self.device = 'seg', torch.device(device)
+        self.tta, self.resize_kw, self.kw = dict(tta), dict(resize or {}), dict(kw)
+        self.rand_augment, self.skipped = None, []
+        dirs = self.tta.get('flip_direction', 'horizontal')
+        if self.tta.get('flip', False):
+            for d in (dirs if isinstance(dirs, (list, tuple)) else [dirs]):
+                if d != 'horizontal':
+                    raise NotImplementedError(f"MultiScaleFlipAug(flip_direction={d!r}): the input kernels flip horizontally only")
+        self.views = None if self.tta.get('img_scale') is None else self._plan(None)
+        self._collates = {}
+
+    def _plan(self, img_hw):
+        views = plan_tta_views(img_hw=img_hw, **self.tta)
+        if len(views) > SEG_TTA_MAX_VIEWS:
+            raise ValueError(f'MultiScaleFlipAug plans {len(views)} views: rscotr_seg_predict_tta_u8 takes at most '
+                             f'{SEG_TTA_MAX_VIEWS}')
+        return views
+
+    def _collate(self, scale, flip):
+        c = self._collates.get((scale, flip))
+        if c is None:
+            c = self._collates[(scale, flip)] = DeviceCollate(
+                'seg', self.device, **dict(self.kw, labels=False, flip_prob=1.0 if flip else 0.0,
+                                           resize=dict(self.resize_kw, img_scale=scale)))
+        return c
+
+    def __call__(self, samples, rng=None, py_rng=None):
+        shapes = {tuple(s['img'].shape) for s in samples}
+        if len(shapes) != 1:
+            raise ValueError(f'test-time augmentation takes batches of one image shape, got {sorted(shapes)}')
+        views = self.views if self.views is not None else self._plan(next(iter(shapes))[:2])
+        imgs, metas = [], []
+        for scale, flip, _ in views:
+            batch = self._collate(scale, flip)(samples, rng)
+            imgs.append(batch['img'])
+            metas.append(batch['img_metas'])
+        return dict(img=imgs, img_metas=metas)
+
+
 _PASSIVE = {'LoadImageFromFile', 'ImageToTensor', 'ToTensor', 'DefaultFormatBundle', 'Collect', 'Normalize'}
 
 
@@ -930,16 +1007,17 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
     Understood: LoadImageFromFile, LoadAnnotations (reduce_zero_label), Resize (mmseg / mmdet img_scale + ratio_range +
     keep_ratio; mmcls size + backend + interpolation), RandomResizedCrop, RandomCrop, RandomFlip, PhotoMetricDistortion,
     RandomErasing, Normalize, Pad, ImageToTensor, ToTensor, DefaultFormatBundle, Collect, MultiScaleFlipAug (its single
-    scale and its transforms; flip=False) and RandAugment when `policies` is a non-empty list of the 13 implemented types
+    scale and its transforms; flip=False — for task 'seg' also flip=True, `img_ratios` and several scales, up to
+    SEG_TTA_MAX_VIEWS views: the result is then a SegTTACollate) and RandAugment when `policies` is a non-empty list of the 13 implemented types
     (RA_OPS) whose warps ask for 'nearest' or 'bicubic'.  Anything else (a RandAugment with an empty list, another policy or
     another interpolation among them) raises NotImplementedError naming it, unless unsupported='skip': then it is left out and
     listed in `collate.skipped`, and the random stream no longer matches the reference's (the skipped transform's draws are
     not made)."""
     assert unsupported in ('raise', 'skip')
-    kw, skipped, norm = dict(flip_prob=0.0), [], None
+    kw, skipped, norm, tta = dict(flip_prob=0.0), [], None, None
 
     def visit(t, scale=None):
-        nonlocal norm
+        nonlocal norm, tta
         t = dict(t)
         typ = t.pop('type')
         if typ in _PASSIVE:
@@ -948,13 +1026,21 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
         elif typ == 'LoadAnnotations':
             kw['reduce_zero_label'] = bool(t.get('reduce_zero_label', False))
         elif typ == 'MultiScaleFlipAug':
-            if t.get('flip', False):
-                raise NotImplementedError('MultiScaleFlipAug(flip=True)')
-            sc = t.get('img_scale')
-            if isinstance(sc, list):
-                if len(sc) != 1:
-                    raise NotImplementedError('MultiScaleFlipAug with several scales')
-                sc = sc[0]
+            sc, ratios = t.get('img_scale'), t.get('img_ratios')
+            rl = [] if ratios is None else (list(ratios) if isinstance(ratios, (list, tuple)) else [ratios])
+            # (one ratio other than 1.0 is a one-view plan: the planner applies it, the single-view path below would not)
+            several = len(rl) > 1 or any(r != 1.0 for r in rl) or (isinstance(sc, list) and len(sc) != 1)
+            if task == 'seg' and (t.get('flip', False) or several):  # test-time augmentation: SegTTACollate plans the views
+                tta = dict(img_scale=sc if sc is None or isinstance(sc, list) else tuple(sc), img_ratios=ratios,
+                           flip=bool(t.get('flip', False)), flip_direction=t.get('flip_direction', 'horizontal'))
+                sc = None
+            else:
+                if t.get('flip', False):
+                    raise NotImplementedError('MultiScaleFlipAug(flip=True)')
+                if isinstance(sc, list):
+                    if len(sc) != 1:
+                        raise NotImplementedError('MultiScaleFlipAug with several scales')
+                    sc = sc[0]
             for u in t.get('transforms', []):
                 visit(u, tuple(sc) if sc is not None else None)
         elif typ == 'Resize':
@@ -963,6 +1049,12 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
                 kw['resize'] = dict(size=(size, size) if isinstance(size, int) else tuple(size))
             else:
                 sc = t.get('img_scale', scale)
+                if tta is not None:  # (the scale is the view's; the other Resize arguments are kept for every view)
+                    if sc is not None or t.get('ratio_range') is not None:
+                        raise NotImplementedError('Resize with its own img_scale / ratio_range inside a multi-view MultiScaleFlipAug')
+                    kw['tta_resize'] = dict(keep_ratio=t.get('keep_ratio', True))
+                    kw['resize_backend'] = _backend(t)
+                    return
                 if sc is None:  # MultiScaleFlipAug(img_scale=None, img_ratios=[1.0]): the image's own size
                     return
                 if isinstance(sc, list):
@@ -979,6 +1071,8 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
             kw['crop_size'] = (cs, cs) if isinstance(cs, int) else tuple(cs)
             kw['cat_max_ratio'] = t.get('cat_max_ratio', 1.0)
             kw['ignore_index'] = t.get('ignore_index', 255)
+        elif typ == 'RandomFlip' and tta is not None:
+            pass  # (MultiScaleFlipAug sets the flip of every view)
         elif typ == 'RandomFlip':
             kw['flip_prob'] = t.get('flip_prob', t.get('flip_ratio', t.get('prob', 0.0))) or 0.0
         elif typ == 'PhotoMetricDistortion':
@@ -1001,7 +1095,11 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
                                       f"unsupported='skip') leaves it out)")
     for t in pipeline_cfg:
         visit(t)
-    col = DeviceCollate(task, device, img_norm_cfg=norm, **kw)
+    if tta is not None:
+        kw.pop('flip_prob')
+        col = SegTTACollate(device, tta, resize=kw.pop('tta_resize', None), img_norm_cfg=norm, **kw)
+    else:
+        col = DeviceCollate(task, device, img_norm_cfg=norm, **kw)
     col.skipped = skipped
     return col
 
