@@ -245,6 +245,8 @@ class _GroupNormTokens(Function):
         if not (dy.dtype == torch.float32 and dy.dim() == 3 and dy.stride(2) == 1 and dy.stride(1) == C
                 and dy.stride(0) >= L * C and dy.stride(0) % 4 == 0 and dy.data_ptr() % 16 == 0):
             dy = _f32c(dy)
+            if dy.data_ptr() % 16:  # dense already, but carved off an unaligned offset: contiguous() handed it back as it was
+                dy = dy.clone()
         dx = torch.empty_like(x)
         # dgamma / dbeta are ADDED by the kernel: straight into the gradient arena when both parameters are sunk (no
         # zero-filled staging rows, no accumulate launches by autograd)

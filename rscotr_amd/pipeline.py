@@ -811,6 +811,8 @@ class DeviceCollate:
         return offs
 
     def __call__(self, samples, rng=None, py_rng=None):
+        if self.device.type != 'cuda':  # (the launches below would hand host pointers to a kernel wherever a GPU is present)
+            raise RuntimeError(f'DeviceCollate runs HIP kernels: it needs a GPU device, not {self.device}')
         rng = rng or np.random
         if self.rand_augment is not None:
             return self._call_randaug(samples, rng, py_rng or random)
