@@ -517,6 +517,30 @@ int rscotr_upsample_ce_fwd(const float* logit, const int64_t* label, float* lse,
                            void* stream);
 int rscotr_upsample_ce_bwd(const float* logit, const int64_t* label, const float* lse, const float* grad_scale,
                            float* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index, void* stream);
+/* The same loss with mmseg's CrossEntropyLoss(class_weight, avg_non_ignore) options and OHEMPixelSampler(thresh, min_kept)
+ * (additive entries: the two above keep their argument lists and their bits).
+ *   _w_fwd: as _fwd, plus nll (B,H,W) = the pixel's CE (0 where ignored) and pix_weight (B,H,W) = class_weight[label]
+ *     (1 everywhere when class_weight is NULL; 0 where ignored); sums[0] = sum of pix_weight * nll; sums[1], sums[2] as above
+ *     (unweighted counts).  With all-ones weights sums[0] is bit-equal to rscotr_upsample_ce_fwd's.  Same launch count.
+ *   _ohem: pixel sampling on the device, no host read.  Over the valid pixels, prob = exp(-nll); kth = the
+ *     min(kept, N_valid - 1)-th smallest prob (0-based), T = max(kth, thresh); a pixel is kept when prob < T (strict), decided
+ *     on the CE plane as nll > min(k-th largest nll, nll_thresh) with nll_thresh = -log(thresh) from the caller.  A radix
+ *     select over the float bit patterns (4 x (histogram with integer atomics + pick)); N_valid is counted on the device.
+ *     Rewrites pix_weight = kept * class_weight[label] and writes sum_out[0] = sum of pix_weight * nll (fixed order; with every
+ *     valid pixel kept, bit-equal to _w_fwd's sums[0]).  npix = B*H*W < 2^31; any number of equal values.
+ *   _w_bwd: dlogit = grad_scale[0] * d(sum of pix_weight * nll)/d(logit), pix_weight held constant; cells no weighted pixel
+ *     touches are written as exact zeros.
+ *   workspace (_w_fwd and _ohem): rscotr_upsample_ce_w_workspace() bytes. */
+int64_t rscotr_upsample_ce_w_workspace(void);
+int rscotr_upsample_ce_w_fwd(const float* logit, const int64_t* label, const float* class_weight, float* lse, float* nll,
+                             float* pix_weight, float* sums, int B, int C, int h, int w, int H, int W, int ignore_index,
+                             float* workspace, int64_t workspace_bytes, void* stream);
+int rscotr_upsample_ce_ohem(const int64_t* label, const float* class_weight, const float* nll, float* pix_weight,
+                            float* sum_out, int64_t npix, int C, int ignore_index, int64_t kept, float nll_thresh,
+                            float* workspace, int64_t workspace_bytes, void* stream);
+int rscotr_upsample_ce_w_bwd(const float* logit, const int64_t* label, const float* lse, const float* pix_weight,
+                             const float* grad_scale, float* dlogit, int B, int C, int h, int w, int H, int W,
+                             int ignore_index, void* stream);
 
 /* Query position embedding of the DINO decoder (models/multi/bbox_head/transformer.py:43-76): pos (rows,4) = (x,y,w,h)
  * -> out (rows,512) = [emb(y)|emb(x)|emb(w)|emb(h)], emb(v)[2i] = sin(2 pi v / 10000^(2i/128)), [2i+1] = cos.  No

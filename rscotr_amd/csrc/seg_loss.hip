@@ -32,10 +32,16 @@ __device__ __forceinline__ Interp src_index(int d, float scale, int in) {
 }
 
 // one thread per output pixel; classes streamed (online log-sum-exp + running arg-max)
+// WT (class weights / pixel sampling, rscotr_upsample_ce_w_fwd): the pixel's CE is also written to `nll` (0 for an ignored pixel)
+// and its weight cw[label] (1 without class weights, 0 for an ignored pixel) to `pixw`; sums[0] is the WEIGHTED sum.  The
+// unweighted instantiation never touches the three extra pointers.
+template <bool WT>
 __global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(const float* __restrict__ logit,
                                                               const int64_t* __restrict__ label,
                                                               float* __restrict__ lse, float* __restrict__ sums, int B,
-                                                              int C, int h, int w, int H, int W, int ignore) {
+                                                              int C, int h, int w, int H, int W, int ignore,
+                                                              const float* __restrict__ cw, float* __restrict__ nll,
+                                                              float* __restrict__ pixw) {
   const long npix = (long)B * H * W;
   const float sy = (float)h / (float)H, sx = (float)w / (float)W;
   float loss = 0.f, correct = 0.f, valid = 0.f;
@@ -58,7 +64,18 @@ __global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(const float* __res
     }
     const float l = m + __logf(s);
     lse[p] = l;
-    if (lab != ignore) {
+    if constexpr (WT) {
+      float nl = 0.f, pw = 0.f;
+      if (lab != ignore) {
+        nl = l - at_label;
+        pw = (cw && lab >= 0 && lab < C) ? cw[lab] : 1.f;
+        loss = fmaf(pw, nl, loss);
+        valid += 1.f;
+        correct += (arg == (int)lab) ? 1.f : 0.f;
+      }
+      nll[p] = nl;
+      pixw[p] = pw;
+    } else if (lab != ignore) {
       loss += l - at_label;
       valid += 1.f;
       correct += (arg == (int)lab) ? 1.f : 0.f;
@@ -104,11 +121,16 @@ constexpr int UCE_TB = 4;    // cells per block edge
 constexpr int UCE_NB = UCE_TB + 2;
 constexpr int UCE_FP = 48;   // staged footprint rows / columns (40 at x8); larger footprints read labels / lse from global memory
 
+// WT (rscotr_upsample_ce_w_bwd): every pixel's softmax - one-hot is multiplied by pixw[p] (class weight x sampling mask); a
+// pixel of weight 0 is staged as ignored.  The weights of a staged footprint take UCE_FP^2 more floats of LDS (80 KB in all:
+// still two workgroups per CU).
+template <bool WT>
 __global__ __launch_bounds__(512) void upsample_ce_bwd_kernel(const float* __restrict__ logit,
                                                               const int64_t* __restrict__ label,
                                                               const float* __restrict__ lse,
                                                               const float* __restrict__ gscale, float* __restrict__ dlogit,
-                                                              int B, int C, int h, int w, int H, int W, int ignore) {
+                                                              int B, int C, int h, int w, int H, int W, int ignore,
+                                                              const float* __restrict__ pixw) {
   extern __shared__ __attribute__((aligned(16))) float uce_smem[];
   float* sN = uce_smem;                                  // [UCE_NB * UCE_NB][128]   neighbourhood logits of the 128 classes of a pass
   float* sAcc = sN + UCE_NB * UCE_NB * 128;              // [4 groups][UCE_TB * UCE_TB][128]
@@ -116,6 +138,7 @@ __global__ __launch_bounds__(512) void upsample_ce_bwd_kernel(const float* __res
   float* sYl = reinterpret_cast<float*>(sLL + UCE_FP * UCE_FP);    // [UCE_FP][2]  l0, l1 of a footprint row
   int* sYi = reinterpret_cast<int*>(sYl + 2 * UCE_FP);   // [UCE_FP][2]  i0, i1 relative to the block's first cell - 1
   int4* sXT = reinterpret_cast<int4*>(sYi + 2 * UCE_FP);  // [UCE_FP] {i0, i1 (same origin), bits of l0, l1} of a footprint column
+  float* sPW = reinterpret_cast<float*>(sXT + UCE_FP);   // WT only: [UCE_FP * UCE_FP] weight of a footprint pixel
   const int bw = (w + UCE_TB - 1) / UCE_TB, bh = (h + UCE_TB - 1) / UCE_TB;
   const int blk = blockIdx.x;
   const int cx0 = (blk % bw) * UCE_TB, cy0 = ((blk / bw) % bh) * UCE_TB, b = blk / (bw * bh);
@@ -133,7 +156,13 @@ __global__ __launch_bounds__(512) void upsample_ce_bwd_kernel(const float* __res
   if (staged) {
     for (int i = tid; i < ny * nx; i += 512) {
       const long p = ((long)b * H + y_lo + i / nx) * W + x_lo + i % nx;
-      sLL[i] = make_int2((int)label[p], __float_as_int(lse[p] * 1.4426950408889634f));  // (the staged path works in the log2 domain: one v_exp_f32 per pixel and class)
+      if constexpr (WT) {
+        const float pw = pixw[p];
+        sPW[i] = pw;
+        sLL[i] = make_int2(pw == 0.f ? ignore : (int)label[p], __float_as_int(lse[p] * 1.4426950408889634f));
+      } else {
+        sLL[i] = make_int2((int)label[p], __float_as_int(lse[p] * 1.4426950408889634f));  // (the staged path works in the log2 domain: one v_exp_f32 per pixel and class)
+      }
     }
   }
   for (int i = tid; i < min(ny, UCE_FP); i += 512) {
@@ -183,6 +212,7 @@ __global__ __launch_bounds__(512) void upsample_ce_bwd_kernel(const float* __res
         if (!in0 && !in1) continue;
         const int b0 = min(max(ky0, 0), UCE_NB - 1), b1 = min(max(ky1, 0), UCE_NB - 1);
         const int2* llr = sLL + r * nx;
+        const float* pwr = sPW + r * nx;  // (WT only)
         float cs[UCE_TB + 2];  // column sums of this row by block column + 1 (0 and TB + 1: the halo, dropped)
 #pragma unroll
         for (int k = 0; k < UCE_TB + 2; ++k) cs[k] = 0.f;
@@ -200,17 +230,22 @@ __global__ __launch_bounds__(512) void upsample_ce_bwd_kernel(const float* __res
           // one 16-byte column record + one 8-byte pixel record per step, the next step's pair requested before this one is used
           int4 xt_n = sXT[x0];
           int2 ll_n = llr[x0];
+          float pw_n = 0.f;
+          if constexpr (WT) pw_n = pwr[x0];
           for (int xx = x0; xx < x1; ++xx) {
             const int4 xt = xt_n;
             const int2 ll = ll_n;
+            const float pw = pw_n;
             const int xn = min(xx + 1, nx - 1);
             xt_n = sXT[xn];
             ll_n = llr[xn];
+            if constexpr (WT) pw_n = pwr[xn];
             const int lab = sc(ll.x);
             if (lab == ignore) continue;
             const float xl0 = __int_as_float(sc(xt.z)), xl1 = __int_as_float(sc(xt.w));
             const float ls = __int_as_float(sc(ll.y));
-            const float gq = __builtin_amdgcn_exp2f(fmaf(xl1, A1, fmaf(xl0, A0, -ls))) - (c == lab ? 1.f : 0.f);
+            float gq = __builtin_amdgcn_exp2f(fmaf(xl1, A1, fmaf(xl0, A0, -ls))) - (c == lab ? 1.f : 0.f);
+            if constexpr (WT) gq *= scf(pw);
             s0 = fmaf(xl0, gq, s0);
             s1 = fmaf(xl1, gq, s1);
           }
@@ -264,8 +299,14 @@ __global__ __launch_bounds__(512) void upsample_ce_bwd_kernel(const float* __res
           float ls;
           { const long p = ((long)b * H + y_lo + r) * W + x_lo + xx; lab = (int)label[p]; ls = lse[p]; }  // (footprints past the staged size)
           if (lab == ignore) continue;
+          float pw = 1.f;
+          if constexpr (WT) {
+            pw = pixw[((long)b * H + y_lo + r) * W + x_lo + xx];
+            if (pw == 0.f) continue;
+          }
           const float v = yl0 * (xl0 * n00 + xl1 * n01) + yl1 * (xl0 * n10 + xl1 * n11);
-          const float gq = __expf(v - ls) - (c == lab ? 1.f : 0.f);
+          float gq = __expf(v - ls) - (c == lab ? 1.f : 0.f);
+          if constexpr (WT) gq *= pw;
           t00 += yl0 * xl0 * gq; t01 += yl0 * xl1 * gq; t10 += yl1 * xl0 * gq; t11 += yl1 * xl1 * gq;
         }
         flush();
@@ -288,8 +329,115 @@ __global__ __launch_bounds__(512) void upsample_ce_bwd_kernel(const float* __res
   }
 }
 
-constexpr size_t uce_bwd_lds_bytes() {
-  return (size_t)(UCE_NB * UCE_NB * 128 + 4 * UCE_TB * UCE_TB * 128 + 2 * UCE_FP * UCE_FP + 8 * UCE_FP) * 4;
+constexpr size_t uce_bwd_lds_bytes(bool weighted = false) {
+  return (size_t)(UCE_NB * UCE_NB * 128 + 4 * UCE_TB * UCE_TB * 128 + 2 * UCE_FP * UCE_FP + 8 * UCE_FP +
+                  (weighted ? UCE_FP * UCE_FP : 0)) * 4;
+}
+static_assert(2 * uce_bwd_lds_bytes(true) <= 160 * 1024, "two weighted backward workgroups per CU");
+
+// ---- online hard example mining (mmseg OHEMPixelSampler with a probability threshold) ---------------------------------------
+// A valid pixel is kept when prob_p < max(kth, thresh), kth = the min(kept, N_valid - 1)-th smallest prob_p = exp(-nll_p) over
+// the valid pixels.  exp is monotone, so the selection is made on the CE plane itself: nll_p > min(k-th LARGEST nll, -log thresh).
+// The order statistic is a radix select over the order-preserving 32-bit keys of the floats, most significant byte first: a
+// histogram launch (LDS bins, then integer atomics on 256 global bins: order-independent) and a one-workgroup pick launch per
+// byte.  N_valid is the first histogram's total: it never leaves the device.  Any number of equal values lands in one bin.
+constexpr int UCE_SEL_WG = 256;  // grid cap of the histogram and mask launches (one workgroup per CU)
+constexpr int UCE_SEL_WORDS = 4 * 256 + 8;  // four histograms + {prefix, rank, N_valid, bits of the CE threshold}
+
+__device__ __forceinline__ unsigned uce_key(float v) {  // a < b  <=>  key(a) < key(b) (as unsigned; -0 < +0)
+  const unsigned b = __float_as_uint(v);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float uce_unkey(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// pass j counts byte (3 - j) of the keys whose higher bytes equal the prefix picked so far
+__global__ __launch_bounds__(256) void uce_ohem_hist_kernel(const int64_t* __restrict__ label, const float* __restrict__ nll,
+                                                            unsigned* __restrict__ hist, const unsigned* __restrict__ st,
+                                                            long npix, int ignore, int pass) {
+  __shared__ unsigned sh[256];
+  sh[threadIdx.x] = 0u;
+  __syncthreads();
+  const int shift = 24 - 8 * pass;
+  const unsigned prefix = pass ? st[0] : 0u;
+  for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
+    if (label[p] == ignore) continue;
+    const unsigned key = uce_key(nll[p]);
+    if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&sh[(key >> shift) & 255u], 1u);
+  }
+  __syncthreads();
+  if (sh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], sh[threadIdx.x]);
+}
+
+// one workgroup: the bin that holds the wanted rank extends the prefix; the last pass leaves the CE threshold
+__global__ __launch_bounds__(256) void uce_ohem_pick_kernel(const unsigned* __restrict__ hist, unsigned* __restrict__ st,
+                                                            long long kept, float nl_thresh, int pass) {
+  __shared__ unsigned sh[256];
+  sh[threadIdx.x] = hist[threadIdx.x];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  unsigned prefix = 0u, rank = 0u;
+  if (pass == 0) {
+    unsigned n = 0u;
+    for (int i = 0; i < 256; ++i) n += sh[i];
+    st[2] = n;
+    // ascending rank of the min(kept, n - 1)-th largest value
+    if (n) rank = (unsigned)((long long)n - 1 - (kept < (long long)n - 1 ? kept : (long long)n - 1));
+  } else {
+    prefix = st[0];
+    rank = st[1];
+  }
+  unsigned cum = 0u;
+  int b = 0;
+  for (; b < 255; ++b) {
+    if (rank < cum + sh[b]) break;
+    cum += sh[b];
+  }
+  prefix |= (unsigned)b << (24 - 8 * pass);
+  st[0] = prefix;
+  st[1] = rank - cum;
+  if (pass == 3)  // no valid pixel: nothing is greater than +inf
+    st[3] = __float_as_uint(st[2] ? fminf(uce_unkey(prefix), nl_thresh) : __builtin_inff());
+}
+
+// pix_weight = [valid and nll > threshold] * cw[label], and sum pix_weight * nll.  The sum is formed as the forward kernel forms
+// its own — "virtual" workgroup v of nvwg (the forward launch's grid) owns pixels v * 256 + t, + nvwg * 256, ... and leaves
+// partial row v — so a sampler that keeps every valid pixel reproduces the unsampled sum bit for bit, at any grid size here.
+__global__ __launch_bounds__(256) void uce_ohem_mask_kernel(const int64_t* __restrict__ label, const float* __restrict__ cw,
+                                                            const float* __restrict__ nll, const unsigned* __restrict__ st,
+                                                            float* __restrict__ pixw, float* __restrict__ part, long npix,
+                                                            int C, int ignore, int nvwg) {
+  __shared__ float red[4];
+  const float thr = __uint_as_float(st[3]);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int v = blockIdx.x; v < nvwg; v += gridDim.x) {
+    float loss = 0.f;
+    for (long p = (long)v * 256 + threadIdx.x; p < npix; p += (long)nvwg * 256) {
+      const long lab = label[p];
+      const float nl = nll[p];
+      float pw = 0.f;
+      if (lab != ignore && nl > thr) pw = (cw && lab >= 0 && lab < C) ? cw[lab] : 1.f;
+      pixw[p] = pw;
+      loss = fmaf(pw, nl, loss);
+    }
+    loss = wave_sum(loss);
+    __syncthreads();  // (the previous round's read of red)
+    if (lane == 0) red[wv] = loss;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(long)v * 3] = red[0] + red[1] + red[2] + red[3];
+  }
+}
+
+// column 0 of upsample_ce_sums_kernel, in its order
+__global__ __launch_bounds__(256) void uce_fold1_kernel(const float* __restrict__ part, float* __restrict__ out, int nparts) {
+  float a = 0.f;
+  for (int i = threadIdx.x; i < nparts; i += 256) a += part[(long)i * 3];
+  __shared__ float red[4];
+  a = wave_sum(a);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) out[0] = red[0] + red[1] + red[2] + red[3];
 }
 
 // Masked-attention mask of the Mask2Former-style decoder (models/multi/seg_head/mask2former_head.py:126-136 and
@@ -353,7 +501,8 @@ extern "C" int rscotr_upsample_ce_fwd(const float* logit, const int64_t* label, 
     return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_fwd: workspace of rscotr_upsample_ce_workspace() bytes required");
   const long npix = (long)B * H * W;
   const int nwg = (int)std::min<long>((npix + 255) / 256, UCE_MAX_WG);
-  upsample_ce_fwd_kernel<<<nwg, 256, 0, s>>>(logit, label, lse, workspace, B, C, h, w, H, W, ignore_index);
+  upsample_ce_fwd_kernel<false><<<nwg, 256, 0, s>>>(logit, label, lse, workspace, B, C, h, w, H, W, ignore_index, nullptr, nullptr,
+                                                    nullptr);
   upsample_ce_sums_kernel<<<1, 256, 0, s>>>(workspace, sums, nwg);
   return check_launch("rscotr_upsample_ce_fwd");
 }
@@ -369,13 +518,88 @@ extern "C" int rscotr_upsample_ce_bwd(const float* logit, const int64_t* label, 
   if (!logit || !label || !lse || !grad_scale || !dlogit) return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_bwd: null pointer");
   static_assert(UCE_TB == 4, "four row groups write the four cell rows of a block");
   static const bool attr_set = [] {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(upsample_ce_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    hipFuncSetAttribute(reinterpret_cast<const void*>(upsample_ce_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                         (int)uce_bwd_lds_bytes());
     return true;
   }();
   (void)attr_set;
   const int nblk = B * ((h + UCE_TB - 1) / UCE_TB) * ((w + UCE_TB - 1) / UCE_TB);
-  upsample_ce_bwd_kernel<<<nblk, 512, uce_bwd_lds_bytes(), (hipStream_t)stream>>>(logit, label, lse, grad_scale, dlogit, B, C, h,
-                                                                                 w, H, W, ignore_index);
+  upsample_ce_bwd_kernel<false><<<nblk, 512, uce_bwd_lds_bytes(), (hipStream_t)stream>>>(logit, label, lse, grad_scale, dlogit, B,
+                                                                                        C, h, w, H, W, ignore_index, nullptr);
   return check_launch("rscotr_upsample_ce_bwd");
+}
+
+// ---- class weights / avg_non_ignore / OHEM (additive entries; the two above are untouched) -------------------------------------
+// workspace: the forward partial rows, then the select's histograms and state
+extern "C" int64_t rscotr_upsample_ce_w_workspace(void) { return (int64_t)(UCE_MAX_WG * 3 + UCE_SEL_WORDS) * 4; }
+
+extern "C" int rscotr_upsample_ce_w_fwd(const float* logit, const int64_t* label, const float* class_weight, float* lse,
+                                        float* nll, float* pix_weight, float* sums, int B, int C, int h, int w, int H, int W,
+                                        int ignore_index, float* workspace, int64_t workspace_bytes, void* stream) {
+  if (B < 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0)
+    return fail(RSCOTR_E_SHAPE, "rscotr_upsample_ce_w_fwd: bad shape");
+  if (!sums) return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_w_fwd: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  if (B == 0) {
+    hipMemsetAsync(sums, 0, 4 * sizeof(float), s);
+    return RSCOTR_OK;
+  }
+  if (!logit || !label || !lse || !nll || !pix_weight) return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_w_fwd: null pointer");
+  if (!workspace || workspace_bytes < rscotr_upsample_ce_w_workspace())
+    return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_w_fwd: workspace of rscotr_upsample_ce_w_workspace() bytes required");
+  const long npix = (long)B * H * W;
+  const int nwg = (int)std::min<long>((npix + 255) / 256, UCE_MAX_WG);  // (the unweighted launch's grid: same summation order)
+  upsample_ce_fwd_kernel<true><<<nwg, 256, 0, s>>>(logit, label, lse, workspace, B, C, h, w, H, W, ignore_index, class_weight, nll,
+                                                   pix_weight);
+  upsample_ce_sums_kernel<<<1, 256, 0, s>>>(workspace, sums, nwg);
+  return check_launch("rscotr_upsample_ce_w_fwd");
+}
+
+extern "C" int rscotr_upsample_ce_ohem(const int64_t* label, const float* class_weight, const float* nll, float* pix_weight,
+                                       float* sum_out, int64_t npix, int C, int ignore_index, int64_t kept, float nll_thresh,
+                                       float* workspace, int64_t workspace_bytes, void* stream) {
+  if (npix < 0 || npix > 0x7fffffffLL || C <= 0) return fail(RSCOTR_E_SHAPE, "rscotr_upsample_ce_ohem: bad shape");
+  if (kept < 0 || nll_thresh != nll_thresh) return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_ohem: kept >= 0 and a threshold required");
+  if (!sum_out) return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_ohem: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  if (npix == 0) {
+    hipMemsetAsync(sum_out, 0, sizeof(float), s);
+    return RSCOTR_OK;
+  }
+  if (!label || !nll || !pix_weight) return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_ohem: null pointer");
+  if (!workspace || workspace_bytes < rscotr_upsample_ce_w_workspace())
+    return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_ohem: workspace of rscotr_upsample_ce_w_workspace() bytes required");
+  unsigned* hist = reinterpret_cast<unsigned*>(workspace) + UCE_MAX_WG * 3;
+  unsigned* st = hist + 4 * 256;
+  hipMemsetAsync(hist, 0, UCE_SEL_WORDS * sizeof(unsigned), s);
+  const int nsel = (int)std::min<long>((npix + 255) / 256, UCE_SEL_WG);
+  for (int pass = 0; pass < 4; ++pass) {
+    uce_ohem_hist_kernel<<<nsel, 256, 0, s>>>(label, nll, hist + pass * 256, st, npix, ignore_index, pass);
+    uce_ohem_pick_kernel<<<1, 256, 0, s>>>(hist + pass * 256, st, (long long)kept, nll_thresh, pass);
+  }
+  const int nvwg = (int)std::min<long>((npix + 255) / 256, UCE_MAX_WG);
+  uce_ohem_mask_kernel<<<nsel, 256, 0, s>>>(label, class_weight, nll, st, pix_weight, workspace, npix, C, ignore_index, nvwg);
+  uce_fold1_kernel<<<1, 256, 0, s>>>(workspace, sum_out, nvwg);
+  return check_launch("rscotr_upsample_ce_ohem");
+}
+
+extern "C" int rscotr_upsample_ce_w_bwd(const float* logit, const int64_t* label, const float* lse, const float* pix_weight,
+                                        const float* grad_scale, float* dlogit, int B, int C, int h, int w, int H, int W,
+                                        int ignore_index, void* stream) {
+  if (B < 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0)
+    return fail(RSCOTR_E_SHAPE, "rscotr_upsample_ce_w_bwd: bad shape");
+  if (B == 0) return RSCOTR_OK;
+  if (!logit || !label || !lse || !pix_weight || !grad_scale || !dlogit)
+    return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_w_bwd: null pointer");
+  static const bool attr_set = [] {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(upsample_ce_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                        (int)uce_bwd_lds_bytes(true));
+    return true;
+  }();
+  (void)attr_set;
+  const int nblk = B * ((h + UCE_TB - 1) / UCE_TB) * ((w + UCE_TB - 1) / UCE_TB);
+  upsample_ce_bwd_kernel<true><<<nblk, 512, uce_bwd_lds_bytes(true), (hipStream_t)stream>>>(logit, label, lse, grad_scale, dlogit,
+                                                                                           B, C, h, w, H, W, ignore_index,
+                                                                                           pix_weight);
+  return check_launch("rscotr_upsample_ce_w_bwd");
 }

@@ -1,5 +1,7 @@
 """Detection / segmentation loss pieces: box utilities, matching cost, the assignment solvers, focal / box loss sums, the
-fused upsample + cross-entropy."""
+fused upsample + cross-entropy (plain, and with class weights / avg_non_ignore / OHEM)."""
+import math
+
 import torch
 from torch.autograd import Function
 
@@ -229,6 +231,95 @@ def upsample_ce(seg_logit, label, ignore_index=255):
     acc = (sums[1] * 100.0 / (sums[2] + torch.finfo(torch.float32).eps)).reshape(1)
     return loss, acc
 
+
+class _UpsampleCEWeighted(Function):
+    """The fused seg loss with class weights, the avg_non_ignore normaliser and OHEM pixel sampling (rscotr_upsample_ce_w_* /
+    rscotr_upsample_ce_ohem).  norm: 'all' (/ B*H*W), 'valid' (/ (#non-ignored + eps)) or 'sum'; ohem: None or
+    (kept, nll_thresh).  Everything stays on the device: the normaliser and the upstream gradient meet in the device scalar
+    grad_scale."""
+
+    @staticmethod
+    def forward(ctx, logit, label, ignore_index, class_weight, norm, ohem):
+        logit = _f32c(logit)
+        label = label.contiguous()
+        cw = None if class_weight is None else _f32c(class_weight)
+        _chk(logit, label, cw)
+        B, C, h, w = logit.shape
+        H, W = label.shape[-2:]
+        if cw is not None and cw.numel() != C:
+            raise ValueError(f'class_weight has {cw.numel()} entries, the logits have {C} channels')
+        dev = logit.device
+        lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        nll, pixw = torch.empty_like(lse), torch.empty_like(lse)
+        sums = torch.empty(4, dtype=torch.float32, device=dev)
+        nws = lib.rscotr_upsample_ce_w_workspace()
+        ws = _WS.get(nws, dev).data_ptr()
+        with _Prof('upsample_ce_w_fwd', 4 * B * C * h * w + 20 * B * H * W):
+            lib.call('rscotr_upsample_ce_w_fwd', logit.data_ptr(), label.data_ptr(), _ptr(cw), lse.data_ptr(), nll.data_ptr(),
+                     pixw.data_ptr(), sums.data_ptr(), B, C, h, w, H, W, int(ignore_index), ws, nws, _stream())
+        num = sums[0]
+        if ohem is not None:
+            kept, nll_thresh = ohem
+            with _Prof('upsample_ce_ohem', 6 * 12 * B * H * W):
+                lib.call('rscotr_upsample_ce_ohem', label.data_ptr(), _ptr(cw), nll.data_ptr(), pixw.data_ptr(),
+                         sums.data_ptr() + 12, B * H * W, C, int(ignore_index), int(kept), float(nll_thresh), ws, nws, _stream())
+            num = sums[3]
+        denom = None
+        if norm == 'all':
+            loss = num / float(B * H * W)
+        elif norm == 'valid':
+            denom = sums[2] + torch.finfo(torch.float32).eps
+            loss = num / denom
+        else:
+            loss = num.clone()
+        ctx.save_for_backward(logit, label, lse, pixw, denom)
+        ctx.ignore, ctx.norm = int(ignore_index), norm
+        ctx.mark_non_differentiable(sums, pixw)
+        return loss, sums, pixw
+
+    @staticmethod
+    def backward(ctx, g_loss, g_sums, g_pixw):
+        logit, label, lse, pixw, denom = ctx.saved_tensors
+        B, C, h, w = logit.shape
+        H, W = label.shape[-2:]
+        if ctx.norm == 'all':
+            g_loss = g_loss / float(B * H * W)
+        elif ctx.norm == 'valid':
+            g_loss = g_loss / denom
+        gscale = g_loss.reshape(1).float().contiguous()
+        dlogit = torch.empty_like(logit)
+        with _Prof('upsample_ce_w_bwd', 8 * B * C * h * w + 16 * B * H * W):
+            lib.call('rscotr_upsample_ce_w_bwd', logit.data_ptr(), label.data_ptr(), lse.data_ptr(), pixw.data_ptr(),
+                     gscale.data_ptr(), dlogit.data_ptr(), B, C, h, w, H, W, ctx.ignore, _stream())
+        return dlogit, None, None, None, None, None
+
+
+def upsample_ce_weighted(seg_logit, label, ignore_index=255, class_weight=None, avg_non_ignore=False, reduction='mean',
+                         ohem=None):
+    """`upsample_ce` with mmseg's CrossEntropyLoss options and OHEMPixelSampler, still one fused pass over the logits:
+        l_p = s_p * class_weight[y_p] * nll_p over the non-ignored pixels,
+        reduction='mean': sum l / (B*H*W), or / (#non-ignored + eps) with avg_non_ignore;  'sum': sum l;
+        ohem = (thresh, min_kept) or a dict with those keys: s_p = [prob_p < max(kth, thresh)], kth the
+        min(min_kept * B, #non-ignored - 1)-th smallest probability of the label over the non-ignored pixels (found on the
+        device); None: s_p = 1.
+    class_weight: a float tensor of C entries on the logits' device, or None.
+    -> (loss 0-d, acc (1,) as upsample_ce: unweighted and unsampled, pix_weight (B,H,W) = s_p * class_weight[y_p], no gradient)."""
+    if reduction not in ('mean', 'sum'):
+        raise NotImplementedError(f"upsample_ce_weighted: reduction={reduction!r} (only 'mean' and 'sum')")
+    norm = 'sum' if reduction == 'sum' else ('valid' if avg_non_ignore else 'all')
+    sel = None
+    if ohem is not None:
+        thresh, min_kept = (ohem['thresh'], ohem['min_kept']) if isinstance(ohem, dict) else ohem
+        if thresh is None:
+            raise NotImplementedError('upsample_ce_weighted: the loss-ranked OHEM (thresh=None) is not implemented')
+        if min_kept < 0:
+            raise ValueError(f'min_kept must be >= 0, got {min_kept}')
+        sel = (int(min_kept) * seg_logit.shape[0], -math.log(thresh) if thresh > 0 else math.inf)
+    if class_weight is not None and not torch.is_tensor(class_weight):
+        class_weight = torch.as_tensor(class_weight, dtype=torch.float32, device=seg_logit.device)
+    loss, sums, pix_weight = _UpsampleCEWeighted.apply(seg_logit, label, ignore_index, class_weight, norm, sel)
+    acc = (sums[1] * 100.0 / (sums[2] + torch.finfo(torch.float32).eps)).reshape(1)
+    return loss, acc, pix_weight
 
 
 class _DetProposals(Function):

@@ -16,11 +16,56 @@ from .registry import MODELS
 
 @MODELS.register_module()
 class CrossEntropyLoss(nn.Module):
+    """mmseg CrossEntropyLoss as the seg head uses it: the options are stored here and applied by the fused kernels
+    (ops.upsample_ce / ops.upsample_ce_weighted).  class_weight: a list / tuple of floats or the path of a .npy file, one
+    entry per logit channel (checked at the first call)."""
+
     def __init__(self, use_sigmoid=False, use_mask=False, reduction='mean', class_weight=None, loss_weight=1.0,
                  loss_name='loss_ce', avg_non_ignore=False):
         super().__init__()
-        assert not use_sigmoid and not use_mask and class_weight is None and not avg_non_ignore
+        if use_sigmoid or use_mask:
+            raise NotImplementedError('CrossEntropyLoss: use_sigmoid / use_mask are not implemented (softmax CE only)')
+        if reduction not in ('mean', 'sum'):
+            raise NotImplementedError(f"CrossEntropyLoss: reduction={reduction!r} (only 'mean' and 'sum')")
+        if isinstance(class_weight, str):
+            if not class_weight.endswith('.npy'):
+                raise ValueError(f'class_weight file {class_weight!r}: only .npy is read')
+            import numpy as np
+            class_weight = np.load(class_weight).astype('float64').reshape(-1).tolist()
+        elif isinstance(class_weight, (list, tuple)):
+            class_weight = [float(v) for v in class_weight]
+        elif class_weight is not None:
+            raise TypeError(f'class_weight must be a list / tuple of floats or a .npy path, got {type(class_weight).__name__}')
+        self.reduction, self.class_weight, self.avg_non_ignore = reduction, class_weight, bool(avg_non_ignore)
         self.loss_weight, self.loss_name = loss_weight, loss_name
+        self._cw = {}  # device -> tensor (not a buffer: the state dict keeps the reference's keys)
+
+    @property
+    def is_default(self):
+        return self.class_weight is None and not self.avg_non_ignore and self.reduction == 'mean'
+
+    def weight_on(self, device, num_channels):
+        if self.class_weight is None:
+            return None
+        if len(self.class_weight) != num_channels:
+            raise ValueError(f'class_weight has {len(self.class_weight)} entries, the logits have {num_channels} channels')
+        t = self._cw.get(str(device))
+        if t is None:
+            t = self._cw[str(device)] = torch.tensor(self.class_weight, dtype=torch.float32, device=device)
+        return t
+
+
+@MODELS.register_module()
+class OHEMPixelSampler:
+    """mmseg OHEMPixelSampler with a probability threshold: keep the non-ignored pixels whose label probability is below
+    max(thresh, the (min_kept * batch)-th smallest one).  The selection runs on the device inside ops.upsample_ce_weighted."""
+
+    def __init__(self, context=None, thresh=0.7, min_kept=100000):
+        if thresh is None:
+            raise NotImplementedError('OHEMPixelSampler: the loss-ranked variant (thresh=None) is not implemented')
+        if min_kept < 0:
+            raise ValueError(f'OHEMPixelSampler: min_kept must be >= 0, got {min_kept}')
+        self.thresh, self.min_kept = float(thresh), int(min_kept)
 
 
 @MODELS.register_module()
@@ -112,7 +157,7 @@ class Mask2FormerHead(nn.Module):
                  num_transformer_feat_level=4, scheme=1, pixel_decoder=None, enforce_decoder_input_project=False,
                  transformer_decoder=None, positional_encoding=None, ignore_index=255,
                  loss_decode=dict(type='CrossEntropyLoss', use_sigmoid=False, loss_weight=1.0), align_corners=False,
-                 init_cfg=None):
+                 init_cfg=None, sampler=None):
         super().__init__()
         assert scheme == 2, 'the MTL configs use scheme=2 (queries are the output channels)'
         assert not align_corners
@@ -137,7 +182,20 @@ class Mask2FormerHead(nn.Module):
             nn.Linear(feat_channels, feat_channels), nn.ReLU(inplace=True),
             nn.Linear(feat_channels, feat_channels), nn.ReLU(inplace=True),
             nn.Linear(feat_channels, out_channels))
-        self.loss_decode = MODELS.build(loss_decode)
+        # a dict or a list of dicts, as mmseg's BaseDecodeHead takes it (mask2former_head.py:85-93); no parameters, no keys
+        cfgs = list(loss_decode) if isinstance(loss_decode, (list, tuple)) else [loss_decode]
+        for c in cfgs:
+            if not isinstance(c, dict) or c.get('type') != 'CrossEntropyLoss':
+                name = c.get('type') if isinstance(c, dict) else type(c).__name__
+                raise NotImplementedError(f'loss_decode type {name!r}: the fused seg loss implements CrossEntropyLoss only')
+        built = [MODELS.build(c) for c in cfgs]
+        self.loss_decode = nn.ModuleList(built) if isinstance(loss_decode, (list, tuple)) else built[0]
+        self.sampler = None
+        if sampler is not None:
+            if not isinstance(sampler, dict) or sampler.get('type') != 'OHEMPixelSampler':
+                name = sampler.get('type') if isinstance(sampler, dict) else type(sampler).__name__
+                raise NotImplementedError(f'sampler type {name!r}: only OHEMPixelSampler is implemented')
+            self.sampler = MODELS.build(sampler)
 
     def init_weights(self):
         self.pixel_decoder.init_weights()
@@ -204,8 +262,24 @@ class Mask2FormerHead(nn.Module):
         return self(shared_encoder, neck_feats, backbone_feats, img_metas)
 
     def losses(self, seg_logit, seg_label):
-        loss, acc = ops.upsample_ce(seg_logit, seg_label.squeeze(1), self.ignore_index)
-        return {self.loss_decode.loss_name: loss * self.loss_decode.loss_weight, 'acc_seg': acc}
+        entries = list(self.loss_decode) if isinstance(self.loss_decode, nn.ModuleList) else [self.loss_decode]
+        if self.sampler is None and len(entries) == 1 and entries[0].is_default:
+            loss, acc = ops.upsample_ce(seg_logit, seg_label.squeeze(1), self.ignore_index)
+            return {entries[0].loss_name: loss * entries[0].loss_weight, 'acc_seg': acc}
+        # any option set: one fused call per entry (entries of one name add up, as in BaseDecodeHead.losses)
+        label = seg_label.squeeze(1)
+        ohem = None if self.sampler is None else (self.sampler.thresh, self.sampler.min_kept)
+        out, acc_seg = {}, None
+        for ld in entries:
+            loss, acc, _ = ops.upsample_ce_weighted(
+                seg_logit, label, self.ignore_index, class_weight=ld.weight_on(seg_logit.device, seg_logit.shape[1]),
+                avg_non_ignore=ld.avg_non_ignore, reduction=ld.reduction, ohem=ohem)
+            loss = loss * ld.loss_weight
+            out[ld.loss_name] = out[ld.loss_name] + loss if ld.loss_name in out else loss
+            if acc_seg is None:
+                acc_seg = acc
+        out['acc_seg'] = acc_seg
+        return out
 
     def forward_train(self, neck_feats, backbone_feats, img_metas, gt_semantic_seg, shared_encoder, record=None):
         seg_logits = self.forward(shared_encoder, neck_feats, backbone_feats, img_metas, record)
