@@ -1,6 +1,6 @@
 """NumPy restatement (test infrastructure only) of the resampling and colour transforms of the reference's dataset configs,
-applied per sample in the reference's order with its random draws, for the device path of rscotr_amd/pipeline.py
-(`rscotr_img_aug_u8`).  Written apart from pipeline.py on purpose: its tables are not reused here, so a host-side table bug
+applied per sample in the reference's order with its random draws, for the device path of rscotr_amd/pipeline/
+(`rscotr_img_aug_u8`).  Written apart from the pipeline package on purpose: its tables are not reused here, so a host-side table bug
 shows up as a mismatch.  Crop / flip / normalize / pad are oracle/pipeline.py's.
 
 mmcv 1.6.1 / mmseg 0.28 / mmdet 2.25.1 / mmcls (unpinned upstream) are not installed; what they do is restated below.

@@ -1,6 +1,6 @@
 """NumPy restatement (test infrastructure only) of mmcls RandAugment with the policies of the reference's cls config
-(configs/_base_/cls/rand_aug.py, configs/_base_/cls/resisc_swin_224.py:15-27), for the device path of rscotr_amd/pipeline.py
-(`rscotr_img_frames_u8` -> `rscotr_randaug_u8` -> `rscotr_img_aug_u8`).  Written apart from pipeline.py on purpose: its own
+(configs/_base_/cls/rand_aug.py, configs/_base_/cls/resisc_swin_224.py:15-27), for the device path of rscotr_amd/pipeline/
+(`rscotr_img_frames_u8` -> `rscotr_randaug_u8` -> `rscotr_img_aug_u8`).  Written apart from the pipeline package on purpose: its own
 inverse matrices, its own weight table, its own look-up tables, so a host-side table bug shows up as a mismatch.
 
 mmcls / mmcv / cv2 are not installed.  Everything below is restated from upstream AS REMEMBERED, so parity with mm* / cv2 is by

@@ -1,4 +1,4 @@
-"""Host side of the device resampling / colour stages (rscotr_amd/pipeline.py) and the NumPy oracle they are tested against
+"""Host side of the device resampling / colour stages (rscotr_amd/pipeline/) and the NumPy oracle they are tested against
 (tests/aug_oracle.py), without a GPU: draw order against hand replays of the mm* sequences, resampling tables against the
 oracle and Pillow, oracle known answers, the transform builder and the C ABI declarations."""
 import ctypes
@@ -12,6 +12,7 @@ from PIL import Image
 import aug_oracle as AO
 from rscotr_amd import _lib
 from rscotr_amd import pipeline as P
+from rscotr_amd.pipeline import resample as R
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'aug_pil_bicubic.npz')
 
@@ -159,11 +160,11 @@ def test_host_tables_reproduce_the_oracle(mode):
                nearest=lambda a, w, h: AO.resize_nearest(a, w, h))[mode]
     for H, W, h, w in ((1, 1, 3, 4), (1, 7, 2, 5), (6, 1, 3, 3), (16, 24, 8, 12), (13, 17, 29, 31), (40, 9, 7, 23)):
         img = rng.randint(0, 256, (H, W, 3)).astype(np.uint8)
-        got = _apply(img, P._AXIS[m](W, w, 0, 0, w), P._AXIS[m](H, h, 0, 0, h), m)
+        got = _apply(img, R._AXIS[m](W, w, 0, 0, w), R._AXIS[m](H, h, 0, 0, h), m)
         assert (got == ref(img, w, h)).all(), (H, W, h, w)
     # a window of the resized frame and a source offset (RandomResizedCrop's crop) fold into the entries
     img = rng.randint(0, 256, (30, 40, 3)).astype(np.uint8)
-    got = _apply(img, P._AXIS[m](25, 50, 10, 7, 20), P._AXIS[m](12, 30, 4, 3, 21), m)
+    got = _apply(img, R._AXIS[m](25, 50, 10, 7, 20), R._AXIS[m](12, 30, 4, 3, 21), m)
     assert (got == ref(img[4:16, 10:35], 50, 30)[3:24, 7:27]).all()
 
 
@@ -176,7 +177,7 @@ def test_oracle_pil_bicubic_path_equals_pillow_on_random_crops():
         for w, h in ((224, 224), (3, 4)):  # up and down
             want = np.asarray(Image.fromarray(np.ascontiguousarray(crop)).resize((w, h), Image.BICUBIC))
             assert (AO.resize_bicubic_pil(crop, w, h) == want).all()
-            t = _apply(crop, P._axis_pil_bicubic(crop.shape[1], w, 0, 0, w), P._axis_pil_bicubic(crop.shape[0], h, 0, 0, h),
+            t = _apply(crop, R._axis_pil_bicubic(crop.shape[1], w, 0, 0, w), R._axis_pil_bicubic(crop.shape[0], h, 0, 0, h),
                        P.RESAMPLE_PIL)
             assert (t == want).all()
 

@@ -12,6 +12,7 @@ import torch
 import aug_oracle as AO
 from oracle import pipeline as OP
 from rscotr_amd import pipeline as P
+from rscotr_amd.pipeline import resample as R
 
 pytestmark = pytest.mark.gpu
 MEAN, STD = P.IMG_NORM['mean'], P.IMG_NORM['std']
@@ -239,8 +240,8 @@ def test_all_stages_off_equals_img_prep_bitwise(cuda):
                         device=cuda)
     tabs, ameta, n = [], [], 0
     for b, (x0, y0, cw, ch) in enumerate(wins):
-        xt = P._axis_nearest(W, W, 0, x0, cw)
-        yt = P._axis_nearest(H, H, 0, y0, ch)
+        xt = R._axis_nearest(W, W, 0, x0, cw)
+        yt = R._axis_nearest(H, H, 0, y0, ch)
         ameta.append([b * H * W * 3, H, W, W * 3, cw, ch, flips[b], n, n + xt.size, 1, 1, 0] + [0] * 8)
         tabs += [xt.reshape(-1), yt.reshape(-1)]
         n += xt.size + yt.size
@@ -257,6 +258,26 @@ def test_all_stages_off_equals_img_prep_bitwise(cuda):
     lib.call('rscotr_img_aug_u8', src.data_ptr(), am.data_ptr(), tab.data_ptr(), prm.data_ptr(), c.data_ptr(), B, Hout, Wout,
              mp, sp, 1, st)
     assert torch.equal(a.view(torch.int32), c.view(torch.int32))
+
+
+def test_plain_route_equals_table_route_with_a_do_nothing_stage(cuda):
+    """One host plan under both launches: the same seeded batch through the plain route (rscotr_img_prep_u8 /
+    rscotr_seg_label_prep_u8) and through the table route with a resize to the image's own size (nearest identity entries, no
+    extra draw) is the same batch bit for bit.  The crop is narrower than the image one way and wider the other (crop and pad)."""
+    r = np.random.RandomState(4)
+    seg = [dict(img=r.randint(0, 256, (37, 53, 3)).astype(np.uint8), gt_semantic_seg=r.randint(0, 7, (37, 53)).astype(np.uint8),
+                gt_label=int(r.randint(0, 45))) for _ in range(3)]
+    kw = dict(crop_size=(24, 64), cat_max_ratio=0.75, reduce_zero_label=True, seg_pad_val=5)
+    a = P.DeviceCollate('seg', cuda, **kw)(seg, np.random.RandomState(9))
+    b = P.DeviceCollate('seg', cuda, resize=dict(size=(37, 53)), **kw)(seg, np.random.RandomState(9))
+    assert a['img'].shape == (3, 3, 24, 64) and torch.equal(a['img'].view(torch.int32), b['img'].view(torch.int32))
+    assert torch.equal(a['gt_semantic_seg'], b['gt_semantic_seg'])
+    for k in ('flip', 'img_shape', 'pad_shape'):
+        assert [m[k] for m in a['img_metas']] == [m[k] for m in b['img_metas']]
+    a = P.DeviceCollate('cls', cuda)(seg, np.random.RandomState(9))
+    b = P.DeviceCollate('cls', cuda, resize=dict(size=(37, 53)))(seg, np.random.RandomState(9))
+    assert a['img'].shape == (3, 3, 37, 53) and torch.equal(a['img'].view(torch.int32), b['img'].view(torch.int32))
+    assert torch.equal(a['gt_label'], b['gt_label'])
 
 
 def test_same_seed_same_batch(cuda):

@@ -84,7 +84,7 @@ def test_multi_dataset_test_and_eval_hook(cuda, tmp_path):
 
 
 def _toy_datasets(root, rng):
-    """Three on-disk toy test splits in the layouts the repo's readers take (rscotr_amd/pipeline.py): an image-folder
+    """Three on-disk toy test splits in the layouts the repo's readers take (rscotr_amd/pipeline/datasets.py): an image-folder
     classification set, a COCO-json detection set, a Potsdam-style tile set."""
     import json
     from PIL import Image

@@ -1,4 +1,4 @@
-"""Host side of the device input path (rscotr_amd/pipeline.py): dataset readers on the three on-disk layouts, the random
+"""Host side of the device input path (rscotr_amd/pipeline/): dataset readers on the three on-disk layouts, the random
 decisions drawn like the mm* transforms draw them, and the oracle's own known answers."""
 import json
 import os
@@ -67,9 +67,9 @@ def test_random_decisions_follow_the_reference_draw_order():
     rng = np.random.RandomState(5)
     oy, ox = rng.randint(0, 25), rng.randint(0, 35)
     want = (ox, oy, 16, 16)
-    assert c._crop_window(img, None, np.random.RandomState(5)) == want
+    assert c._crop_window_hw(*img.shape[:2], None, np.random.RandomState(5)) == want
     # an image smaller than the crop is taken whole (and padded on the device)
-    assert c._crop_window(np.zeros((10, 12, 3), np.uint8), None, np.random.RandomState(1)) == (0, 0, 12, 10)
+    assert c._crop_window_hw(10, 12, None, np.random.RandomState(1)) == (0, 0, 12, 10)
     # cat_max_ratio: a window dominated by one class is re-drawn (up to 10 times, then the last draw is kept)
     seg = np.ones((40, 50), np.uint8)
     seg[:20] = 2                      # two classes split at row 20: windows with y0 in 5..19 hold both
@@ -84,7 +84,7 @@ def test_random_decisions_follow_the_reference_draw_order():
         frac = max((w == 1).mean(), (w == 2).mean())
         if frac < 0.75:
             break
-    assert c2._crop_window(img, seg, np.random.RandomState(0)) == want
+    assert c2._crop_window_hw(*img.shape[:2], seg, np.random.RandomState(0)) == want
     # raw label 0 is the ignore index after reduce_zero_label: a window of {0, 1} counts as single-class
     seg0 = np.zeros((40, 50), np.uint8)
     seg0[:, 25:] = 1
@@ -93,7 +93,7 @@ def test_random_decisions_follow_the_reference_draw_order():
     for _ in range(11):
         oy, ox = r.randint(0, 25), r.randint(0, 35)
         last = (ox, oy, 16, 16)
-    assert c2._crop_window(img, seg0, np.random.RandomState(3)) == last  # all 11 draws used
+    assert c2._crop_window_hw(*img.shape[:2], seg0, np.random.RandomState(3)) == last  # all 11 draws used
 
 
 def test_collate_fails_loudly_without_gpu():

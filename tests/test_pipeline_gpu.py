@@ -63,7 +63,7 @@ def test_seg_batches_crop_flip_pad_labels(cuda, seed):
     r2 = np.random.RandomState(seed + 7)
     wins, flips = [], []
     for x in s:
-        wins.append(c._crop_window(x['img'], x['gt_semantic_seg'], r2))
+        wins.append(c._crop_window_hw(*x['img'].shape[:2], x['gt_semantic_seg'], r2))
         flips.append(bool(r2.rand() < 0.5))
     b = c(s, np.random.RandomState(seed + 7))
     assert [m['flip'] for m in b['img_metas']] == flips

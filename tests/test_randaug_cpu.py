@@ -1,4 +1,4 @@
-"""Host side of the device RandAugment stage (rscotr_amd/pipeline.py) and the NumPy oracle it is tested against
+"""Host side of the device RandAugment stage (rscotr_amd/pipeline/randaug.py) and the NumPy oracle it is tested against
 (tests/randaug_oracle.py), without a GPU: draw order and counts on both generators, the magnitude mapping, the oracle's point
 operations against Pillow, the warps against closed forms, the host's integer tables against the oracle, the transform builder
 and the C ABI declarations."""
@@ -13,6 +13,7 @@ import pytest
 import randaug_oracle as RO
 from rscotr_amd import _lib
 from rscotr_amd import pipeline as P
+from rscotr_amd.pipeline import randaug as RA
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'randaug_pil.npz')
 
@@ -132,7 +133,7 @@ def test_magnitude_mapping_every_policy_and_gauss_clamp():
             if p['type'] in want:
                 assert m == pytest.approx(want[p['type']][li], abs=1e-12)
                 assert m == RO.magnitude(p, level, 10)
-                row = col._ra_meta_row(d['ra'][0], p, 61, 37, 4)
+                row = RA.ra_meta_row(d['ra'][0], p, 61, 37, 4)
                 if p['type'] == 'Posterize':
                     assert 8 - row[3] == (4, 1, 0)[li]  # reaches 1 and 0 bits
                 if p['type'] == 'Solarize':
@@ -255,7 +256,7 @@ def test_weight_tables_sum_to_one_and_agree():
 
 def _device_warp(img, entry, p, w, h):
     """What rscotr_randaug_u8 computes for a warp from the host's tables (include/rscotr.h)."""
-    t = P._ra_warp_table(entry[3], w, h, p['interpolation'] == 'bicubic').astype(np.int64)
+    t = RA._ra_warp_table(entry[3], w, h, p['interpolation'] == 'bicubic').astype(np.int64)
     ad, bd, X0, Y0 = t[:w], t[w:2 * w], t[2 * w:2 * w + h], t[2 * w + h:]
     X, Y = X0[:, None] + ad[None], Y0[:, None] + bd[None]
     pad, src = np.array(p['pad_val'], np.int64), img.astype(np.int64)
