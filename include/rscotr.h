@@ -30,7 +30,7 @@ extern "C" {
 /* ABI revision: bumped whenever an exported entry changes its argument list (round 5 inserted amax_out / nbytes before
  * `stream` in the LayerNorm, window-attention, MSDA backward, pack4, splitk_flush and grouped-dW entries = revision 6;
  * round 6 = 7; 11 added the resampling input entries rscotr_img_aug_u8 / rscotr_seg_label_aug_u8; the
- * evaluation entries since — seg_predict / seg_areas, det_decode / det_match, seg_predict_tta — are additive and change no
+ * evaluation entries since — seg_predict / seg_areas, det_decode / det_match, seg_predict_tta, seg_predict_slide — are additive and change no
  * argument list, so they keep 11: a library without them fails to bind by name).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
  * its first call (rscotr_amd/_lib.py does) — a stale .so would take a stream handle for a pointer. */
 #define RSCOTR_ABI_VERSION 11
@@ -802,6 +802,26 @@ int rscotr_seg_areas_u8(const uint8_t* pred, const uint8_t* gt, int64_t* out, in
  * C > 255, a non-positive size, a crop larger than its canvas, C * h * w >= 2^31, B > 65535; RSCOTR_E_ARG: a null pointer or
  * logit address, another flip value.  Every check precedes the first HIP call. */
 int rscotr_seg_predict_tta_u8(const int64_t* views, uint8_t* out, int V, int B, int C, int Ho, int Wo, void* stream);
+
+/* Sliding-window segmentation inference (csrc/seg_eval.hip; mmseg EncoderDecoder.slide_inference, test mode 'slide'; an
+ * additive entry: the ABI revision is unchanged).
+ *
+ * rscotr_seg_predict_slide_u8: the merge of the windows' logits, the rescale, the flip and the arg-max in one launch, no
+ * canvas-sized tensor, no atomics.  The window grid is derived from (H, W) (the input canvas), the crop (ch, cw) and the stride
+ * (sy, sx): per axis g = max(n - crop + stride - 1, 0) / stride + 1 windows, window i spanning [a, b) with
+ * b = min(i * stride + crop, n), a = max(b - crop, 0) (the last one shifted back inside; one whole-axis window where n < crop),
+ * so every window has the size (min(ch, H), min(cw, W)).  logit: device fp32 (Gy * Gx * B, C, h, w), contiguous: the windows
+ * in visiting order (row-major, y outer), the batch innermost.  Canvas value of a pixel and channel: the fp32 sum, in window
+ * order, over the windows covering the pixel of the window's logits resampled to the window size (ATen bilinear,
+ * align_corners = False, as rscotr_seg_predict_u8), divided (IEEE) by their number.  rescale != 0: the canvas is cropped to
+ * (hs, ws) (img_shape) and resampled to (Ho, Wo) (ori_shape), out is uint8 (B, Ho, Wo), every output pixel composing the outer
+ * taps over the canvas values; rescale == 0: hs, ws, Ho, Wo are ignored and out is uint8 (B, H, W).  No softmax (monotone).
+ * Arg-max and flip as rscotr_seg_predict_u8.  The windows are summed in a fixed order: the result is bit-reproducible.  The
+ * number of windows over a pixel is not limited.  RSCOTR_E_SHAPE: C > 255, a non-positive size, a stride larger than the crop on
+ * an axis where the canvas exceeds the crop (uncovered pixels), (hs, ws) larger than the canvas, C * h * w >= 2^31,
+ * Gy * Gx * B >= 2^31, B > 65535; RSCOTR_E_ARG: a null pointer, another flip value.  Every check precedes the first HIP call. */
+int rscotr_seg_predict_slide_u8(const float* logit, uint8_t* out, int B, int C, int h, int w, int H, int W, int ch, int cw, int sy,
+                                int sx, int rescale, int hs, int ws, int Ho, int Wo, int flip, void* stream);
 
 /* Detection evaluation on the device (csrc/det_eval.hip): the inference tail of DINOHead._get_bboxes_single and
  * COCOeval.evaluateImg as rscotr_amd/metrics.py `_evaluate_img` states it (additive entries: no argument list changed, so the ABI

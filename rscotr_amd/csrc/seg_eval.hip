@@ -1,5 +1,5 @@
-// Segmentation evaluation on the device (include/rscotr.h: rscotr_seg_predict_u8, rscotr_seg_predict_tta_u8,
-// rscotr_seg_areas_u8).
+// Segmentation evaluation on the device (include/rscotr.h: rscotr_seg_predict_u8, rscotr_seg_predict_slide_u8,
+// rscotr_seg_predict_tta_u8, rscotr_seg_areas_u8).
 //
 // seg_predict: MTL.whole_inference_seg + the test-time flip + arg-max over channels in one launch.  The head's logits
 // (B, C, h, w) are a few MB and stay in L2; every output pixel composes the two bilinear resamplings of the torch chain
@@ -19,8 +19,24 @@
 // save 32 L1 / L2 hits per channel starves the latency hiding that those very loads need.  The view table rides in the kernel
 // arguments (scalar loads, no device table).
 //
+// seg_predict_slide: mmseg slide_inference (test mode 'slide') + rescale + flip + arg-max in one launch over the logits of ALL
+// windows, (Gy Gx B, C, h, w) in visiting order.  The grid is regular, so the kernel derives it from (H, W, crop, stride): the
+// windows covering a canvas coordinate are a contiguous index range per axis (only the last window of an axis is shifted back).
+// Thread layout as seg_predict.  Per channel, in registers: the in-order sum over the covering windows of the window's 4-tap
+// value, divided by their number, at the one canvas position (no rescale) or at the four positions of the outer taps, then the
+// running arg-max; no canvas-sized tensor, no atomics.  The number of covering windows is dynamic (crop / stride is the user's),
+// so the per-axis taps of (canvas coordinate, window), which do not depend on the channel, cannot sit in registers: each thread
+// computes them once into a private column of dynamic LDS laid out [slot][pixel of the tile] (conflict-free, no barrier, as
+// the TTA accumulators), 3 words per tap, 2 (Ky + Kx) taps with rescale.  That is 36 KB per 256 pixels at crop 512 / stride
+// 341 (at most 3 windows per axis), against C words per pixel in the TTA kernel: four workgroups per CU still fit, so here the
+// stash is the cheaper side of the trade-off, and the host shrinks the tile (T rows of 64) to keep it under 64 KB.  Where even
+// one row does not fit (more than 42 windows over a pixel's two axes), the same kernel recomputes the taps in the loop.  A
+// pixel under one window without rescale takes the body of seg_predict's plain path.
+//
 // seg_areas: mmseg intersect_and_union of a batch.  Per-workgroup LDS histograms over all 256 byte values, then 64-bit
 // integer adds of the first C bins into the caller-zeroed output: exact in any order.
+#include <algorithm>
+
 #include "common.h"
 
 namespace rscotr {
@@ -192,6 +208,153 @@ __global__ __launch_bounds__(256) void seg_predict_tta_kernel(const TtaViews vie
   out[((long)blockIdx.z * Ho + y) * Wo + x] = (uint8_t)idx;
 }
 
+// ---- test mode 'slide': the windows' logits merged, rescaled and arg-maxed -------------------------------------------------
+// One axis of the window grid (mmseg slide_inference): g windows of `crop` (already min(crop, n)) every `stride`, the last one
+// shifted back inside [0, n).
+struct SlideAxis {
+  int n, crop, stride, g, in;  // in: the logits' extent on this axis
+  float scale;                 // in / crop: every window is resampled to the common window size
+};
+
+// the windows covering canvas coordinate pos: lo .. lo + cnt - 1 (stride <= crop wherever n > crop: cnt >= 1)
+__device__ __forceinline__ void slide_cover(int pos, const SlideAxis& a, int& lo, int& cnt) {
+  lo = pos >= a.crop ? (pos - a.crop) / a.stride + 1 : 0;
+  lo = min(lo, a.g - 1);
+  int hi = min(pos / a.stride, a.g - 2);
+  if (pos >= a.n - a.crop) hi = a.g - 1;  // the shifted last window
+  cnt = hi - lo + 1;
+}
+
+// the tap of canvas coordinate pos in window i: offsets in elements (mul = the axis's element stride) and the upper weight
+struct SlideTap {
+  int o0, o1;
+  float l1;
+};
+
+__device__ __forceinline__ SlideTap slide_tap(int pos, int i, const SlideAxis& a, int mul) {
+  const int start = max(min(i * a.stride + a.crop, a.n) - a.crop, 0);
+  const Tap t = bilinear_tap(pos - start, a.scale, a.in);
+  return SlideTap{t.i0 * mul, t.i1 * mul, t.l1};
+}
+
+// a thread's stash column: word `slot` of the thread lives at stash[slot * cols]
+__device__ __forceinline__ void stash_put(int* __restrict__ stash, int cols, int slot, const SlideTap& t) {
+  stash[(3 * slot) * cols] = t.o0;
+  stash[(3 * slot + 1) * cols] = t.o1;
+  stash[(3 * slot + 2) * cols] = __float_as_int(t.l1);
+}
+
+__device__ __forceinline__ SlideTap stash_get(const int* __restrict__ stash, int cols, int slot) {
+  return SlideTap{stash[(3 * slot) * cols], stash[(3 * slot + 1) * cols], __int_as_float(stash[(3 * slot + 2) * cols])};
+}
+
+// One canvas position of one channel: preds (zeros) += the window's resampled logits, in window order (y outer), / count.
+// p: channel c of window 0 of this image; wstride: elements between consecutive windows (B C h w).  ys / xs: first stash slot
+// of this position's y / x taps (kStash), else the taps are recomputed from (Y, X).
+template <bool kStash>
+__device__ __forceinline__ float slide_canvas(const float* __restrict__ p, long wstride, int Gx, int Y, int X, int ylo, int ny,
+                                              int xlo, int nx, const SlideAxis& ay, const SlideAxis& ax, const int* __restrict__ stash,
+                                              int cols, int ys, int xs) {
+  float sum = 0.f;
+  for (int iy = 0; iy < ny; ++iy) {
+    const SlideTap ty = kStash ? stash_get(stash, cols, ys + iy) : slide_tap(Y, ylo + iy, ay, ax.in);
+    const float hl0 = 1.f - ty.l1;
+    const float* __restrict__ q = p + ((long)(ylo + iy) * Gx + xlo) * wstride;
+    for (int ix = 0; ix < nx; ++ix, q += wstride) {
+      const SlideTap tx = kStash ? stash_get(stash, cols, xs + ix) : slide_tap(X, xlo + ix, ax, 1);
+      sum += blend(hl0, ty.l1, 1.f - tx.l1, tx.l1, q[ty.o0 + tx.o0], q[ty.o0 + tx.o1], q[ty.o1 + tx.o0], q[ty.o1 + tx.o1]);
+    }
+  }
+  return __fdiv_rn(sum, (float)(ny * nx));
+}
+
+// block (64, T).  kStash: 3 * kP * (KY + KX) * 64 T words of dynamic LDS, kP = 2 canvas coordinates per axis with rescale, else 1;
+// KY / KX: the host's bound on the windows covering one coordinate.  Thread-private columns: no barrier.
+template <bool kRescale, bool kStash>
+__global__ __launch_bounds__(256) void seg_predict_slide_kernel(const float* __restrict__ logit, uint8_t* __restrict__ out, int B, int C,
+                                                                SlideAxis ay, SlideAxis ax, int KY, int KX, int hs, int ws, int Ho,
+                                                                int Wo, int flip) {
+  extern __shared__ __attribute__((aligned(16))) int slide_stash[];
+  const int x = blockIdx.x * 64 + threadIdx.x;
+  const int y = blockIdx.y * blockDim.y + threadIdx.y;
+  if (x >= Wo || y >= Ho) return;
+  const int px = flip == 1 ? Wo - 1 - x : x;
+  const int py = flip == 2 ? Ho - 1 - y : y;
+  const int cols = 64 * blockDim.y;
+  const int* __restrict__ stash = slide_stash + threadIdx.y * 64 + threadIdx.x;
+  const long plane = (long)ay.in * ax.in;
+  const long wstride = (long)B * C * plane;
+  const float* __restrict__ base = logit + (long)blockIdx.z * C * plane;  // image b of window 0
+  uint8_t* __restrict__ dst = out + ((long)blockIdx.z * Ho + y) * Wo + x;
+  constexpr int kP = kRescale ? 2 : 1;
+
+  Tap t2y, t2x;
+  int Ys[kP], Xs[kP], ylo[kP], ny[kP], xlo[kP], nx[kP];
+  if constexpr (kRescale) {
+    t2y = bilinear_tap(py, (float)hs / (float)Ho, hs);
+    t2x = bilinear_tap(px, (float)ws / (float)Wo, ws);
+    Ys[0] = t2y.i0, Ys[1] = t2y.i1, Xs[0] = t2x.i0, Xs[1] = t2x.i1;
+  } else {
+    Ys[0] = py, Xs[0] = px;
+  }
+#pragma unroll
+  for (int j = 0; j < kP; ++j) {
+    slide_cover(Ys[j], ay, ylo[j], ny[j]);
+    slide_cover(Xs[j], ax, xlo[j], nx[j]);
+    ny[j] = min(ny[j], KY);  // (never binds: KY, KX bound the cover; keeps the stash column in its slots)
+    nx[j] = min(nx[j], KX);
+  }
+
+  if constexpr (!kRescale) {
+    if (ny[0] == 1 && nx[0] == 1) {  // one window, no division: seg_predict's plain path on that window's logits
+      const SlideTap ty = slide_tap(py, ylo[0], ay, ax.in), tx = slide_tap(px, xlo[0], ax, 1);
+      const float hl0 = 1.f - ty.l1, wl0 = 1.f - tx.l1;
+      const int o00 = ty.o0 + tx.o0, o01 = ty.o0 + tx.o1, o10 = ty.o1 + tx.o0, o11 = ty.o1 + tx.o1;
+      const float* __restrict__ p = base + ((long)ylo[0] * ax.g + xlo[0]) * wstride;
+      float best = blend(hl0, ty.l1, wl0, tx.l1, p[o00], p[o01], p[o10], p[o11]);
+      int idx = 0;
+#pragma unroll 4
+      for (int c = 1; c < C; ++c) {
+        p += plane;
+        argmax_step(blend(hl0, ty.l1, wl0, tx.l1, p[o00], p[o01], p[o10], p[o11]), c, best, idx);
+      }
+      *dst = (uint8_t)idx;
+      return;
+    }
+  }
+
+  if constexpr (kStash) {
+    int* __restrict__ mine = slide_stash + threadIdx.y * 64 + threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < kP; ++j) {
+      for (int i = 0; i < ny[j]; ++i) stash_put(mine, cols, j * KY + i, slide_tap(Ys[j], ylo[j] + i, ay, ax.in));
+      for (int i = 0; i < nx[j]; ++i) stash_put(mine, cols, kP * KY + j * KX + i, slide_tap(Xs[j], xlo[j] + i, ax, 1));
+    }
+  }
+
+  float best = 0.f;
+  int idx = 0;
+  for (int c = 0; c < C; ++c) {
+    const float* __restrict__ p = base + c * plane;
+    float v;
+    if constexpr (kRescale) {
+      float q[2][2];
+#pragma unroll
+      for (int jy = 0; jy < 2; ++jy)
+#pragma unroll
+        for (int jx = 0; jx < 2; ++jx)
+          q[jy][jx] = slide_canvas<kStash>(p, wstride, ax.g, Ys[jy], Xs[jx], ylo[jy], ny[jy], xlo[jx], nx[jx], ay, ax, stash, cols,
+                                           jy * KY, kP * KY + jx * KX);
+      v = blend(t2y.l0, t2y.l1, t2x.l0, t2x.l1, q[0][0], q[0][1], q[1][0], q[1][1]);
+    } else {
+      v = slide_canvas<kStash>(p, wstride, ax.g, Ys[0], Xs[0], ylo[0], ny[0], xlo[0], nx[0], ay, ax, stash, cols, 0, kP * KY);
+    }
+    if (c == 0) best = v;
+    else argmax_step(v, c, best, idx);
+  }
+  *dst = (uint8_t)idx;
+}
+
 constexpr int kAreaThreads = 256;
 constexpr int kAreaBlocksMax = 64;    // workgroups per image
 constexpr int kAreaPixPerBlock = 4096;
@@ -255,6 +418,50 @@ extern "C" int rscotr_seg_predict_u8(const float* logit, uint8_t* out, int B, in
     seg_predict_kernel<true><<<grid, block, 0, (hipStream_t)stream>>>(logit, out, C, h, w, H, W, hs, ws, Ho, Wo, flip);
   else
     seg_predict_kernel<false><<<grid, block, 0, (hipStream_t)stream>>>(logit, out, C, h, w, H, W, H, W, Ho, Wo, flip);
+  return check_launch(fn);
+}
+
+extern "C" int rscotr_seg_predict_slide_u8(const float* logit, uint8_t* out, int B, int C, int h, int w, int H, int W, int ch, int cw,
+                                           int sy, int sx, int rescale, int hs, int ws, int Ho, int Wo, int flip, void* stream) {
+  const char* fn = "rscotr_seg_predict_slide_u8";
+  if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || ch <= 0 || cw <= 0 || sy <= 0 || sx <= 0)
+    return fail(RSCOTR_E_SHAPE, "%s: non-positive size", fn);
+  if (C > 255) return fail(RSCOTR_E_SHAPE, "%s: C = %d does not fit a uint8 label map (C <= 255)", fn, C);
+  if (flip < 0 || flip > 2) return fail(RSCOTR_E_ARG, "%s: flip must be 0 (none), 1 (horizontal) or 2 (vertical)", fn);
+  if ((H > ch && sy > ch) || (W > cw && sx > cw))
+    return fail(RSCOTR_E_SHAPE, "%s: stride %d x %d larger than the crop %d x %d leaves pixels of the %d x %d canvas uncovered", fn, sy,
+                sx, ch, cw, H, W);
+  if (rescale) {
+    if (hs <= 0 || ws <= 0 || Ho <= 0 || Wo <= 0) return fail(RSCOTR_E_SHAPE, "%s: non-positive size", fn);
+    if (hs > H || ws > W) return fail(RSCOTR_E_SHAPE, "%s: crop %d x %d larger than the canvas %d x %d", fn, hs, ws, H, W);
+  } else {
+    hs = Ho = H;
+    ws = Wo = W;
+  }
+  if ((int64_t)C * h * w > INT32_MAX) return fail(RSCOTR_E_SHAPE, "%s: C * h * w must fit 31 bits", fn);
+  // the window grid of mmseg slide_inference; every window has the size min(crop, image)
+  const int gy = (int)(std::max((int64_t)H - ch + sy - 1, (int64_t)0) / sy) + 1;
+  const int gx = (int)(std::max((int64_t)W - cw + sx - 1, (int64_t)0) / sx) + 1;
+  if ((int64_t)gy * gx * B > INT32_MAX) return fail(RSCOTR_E_SHAPE, "%s: windows * B must fit 31 bits", fn);
+  if (!logit || !out) return fail(RSCOTR_E_ARG, "%s: null pointer", fn);
+  const int wh = std::min(ch, H), ww = std::min(cw, W);
+  const SlideAxis ay{H, wh, sy, gy, h, (float)h / (float)wh}, ax{W, ww, sx, gx, w, (float)w / (float)ww};
+  // at most ceil(crop / stride) unshifted windows and the shifted last one cover a coordinate
+  const int KY = (int)std::min((int64_t)gy, ((int64_t)wh + sy - 1) / sy + 1), KX = (int)std::min((int64_t)gx, ((int64_t)ww + sx - 1) / sx + 1);
+  const int64_t per_row = (int64_t)3 * (rescale ? 2 : 1) * ((int64_t)KY + KX) * 64 * sizeof(int);  // stash bytes of 64 pixels
+  const bool stash = per_row <= 65536;  // (the 64 KB a launch may ask for without opting in)
+  const int T = !stash || 4 * per_row <= 65536 ? 4 : 2 * per_row <= 65536 ? 2 : 1;
+  if (B > 65535 || (Ho + T - 1) / T > 65535) return fail(RSCOTR_E_SHAPE, "%s: B <= 65535 and Ho <= %d", fn, 65535 * T);
+  const dim3 grid((Wo + 63) / 64, (Ho + T - 1) / T, B), block(64, T);
+  const size_t shm = stash ? (size_t)per_row * T : 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (rescale) {
+    if (stash) seg_predict_slide_kernel<true, true><<<grid, block, shm, st>>>(logit, out, B, C, ay, ax, KY, KX, hs, ws, Ho, Wo, flip);
+    else seg_predict_slide_kernel<true, false><<<grid, block, 0, st>>>(logit, out, B, C, ay, ax, KY, KX, hs, ws, Ho, Wo, flip);
+  } else {
+    if (stash) seg_predict_slide_kernel<false, true><<<grid, block, shm, st>>>(logit, out, B, C, ay, ax, KY, KX, hs, ws, Ho, Wo, flip);
+    else seg_predict_slide_kernel<false, false><<<grid, block, 0, st>>>(logit, out, B, C, ay, ax, KY, KX, hs, ws, Ho, Wo, flip);
+  }
   return check_launch(fn);
 }
 

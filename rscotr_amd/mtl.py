@@ -246,11 +246,63 @@ class MTL(nn.Module):
                                                         mode='bilinear', align_corners=self.seg_head.align_corners)
         return seg_logit
 
+    def _seg_test_mode(self):
+        mode = self.test_cfg['seg']['mode']
+        assert mode in ['whole', 'slide'], f"test_cfg['seg']['mode'] must be 'whole' or 'slide', got {mode!r}"
+        return mode
+
+    def slide_window_logits(self, img, img_meta):
+        """Test mode 'slide' (mmseg EncoderDecoder.slide_inference): the head's logits of every window of the input, one
+        tensor (len(windows) * B, C, h, w) in visiting order with the batch innermost (the layout of ops.seg_predict_slide),
+        and the windows.  test_cfg['seg']: `crop_size` and `stride` as mmseg; `window_batch` (ours, default 1) windows are
+        stacked into one forward pass.  Every pass writes into the one preallocated tensor."""
+        cfg = self.test_cfg['seg']
+        B = img.shape[0]
+        windows = ops.slide_windows(img.shape[2], img.shape[3], cfg['crop_size'], cfg['stride'])
+        step = int(cfg.get('window_batch', 1))
+        if step < 1:
+            raise ValueError(f"test_cfg['seg']['window_batch'] must be a positive integer, got {cfg.get('window_batch')!r}")
+        logits = None
+        for k in range(0, len(windows), step):
+            group = windows[k:k + step]
+            if k:
+                ops.RANGES.begin(img.device)  # (every pass is a forward pass of its own)
+            crops = [img[:, :, y1:y2, x1:x2] for y1, y2, x1, x2 in group]
+            crop = crops[0].contiguous() if len(crops) == 1 else torch.cat(crops, 0)
+            neck_feature, backbone_feature = self.extract_feat(crop)
+            part = self.seg_head.forward_test(neck_feature, backbone_feature, list(img_meta) * len(group), self.shared_encoder)
+            if logits is None:
+                logits = part.new_empty((len(windows) * B,) + tuple(part.shape[1:]))
+            logits[k * B:(k + len(group)) * B].copy_(part)
+        return logits, windows
+
+    def slide_inference_seg(self, img, img_meta, rescale):
+        """mmseg EncoderDecoder.slide_inference in torch ops on the input's device: every window's logits resampled to the
+        window, summed into a canvas-sized tensor in visiting order and divided by the per-pixel window count; with `rescale`
+        cropped to img_shape (as whole_inference_seg) and resampled to ori_shape."""
+        interpolate = torch.nn.functional.interpolate
+        logits, windows = self.slide_window_logits(img, img_meta)
+        B, _, H, W = img.shape
+        preds = logits.new_zeros((B, logits.shape[1], H, W))
+        count = logits.new_zeros((1, 1, H, W))
+        for k, (y1, y2, x1, x2) in enumerate(windows):
+            preds[:, :, y1:y2, x1:x2] += interpolate(logits[k * B:(k + 1) * B], size=(y2 - y1, x2 - x1), mode='bilinear',
+                                                     align_corners=self.seg_head.align_corners)
+            count[:, :, y1:y2, x1:x2] += 1
+        preds = preds / count  # (ops.slide_windows has refused a grid that leaves a pixel uncovered)
+        if rescale:
+            h, w = img_meta[0]['img_shape'][:2]
+            preds = interpolate(preds[:, :, :h, :w], size=tuple(img_meta[0]['ori_shape'][:2]), mode='bilinear',
+                                align_corners=self.seg_head.align_corners)
+        return preds
+
     def inference_seg(self, img, img_meta, rescale):
-        assert self.test_cfg['seg']['mode'] in ['whole']
+        mode = self._seg_test_mode()
         ori_shape = img_meta[0]['ori_shape']
         assert all(_['ori_shape'] == ori_shape for _ in img_meta)
-        output = torch.softmax(self.whole_inference_seg(img, img_meta, rescale), dim=1)
+        seg_logit = self.slide_inference_seg(img, img_meta, rescale) if mode == 'slide' else \
+            self.whole_inference_seg(img, img_meta, rescale)
+        output = torch.softmax(seg_logit, dim=1)
         if img_meta[0].get('flip', False):
             direction = img_meta[0]['flip_direction']
             assert direction in ['horizontal', 'vertical']
@@ -258,17 +310,24 @@ class MTL(nn.Module):
         return output
 
     def predict_seg_device(self, img, img_meta, rescale):
-        """inference_seg + argmax as ONE launch on the head's logits (ops.seg_predict): uint8 (B, Ho, Wo) on the device,
-        no up-sampled tensor, no softmax (monotone), no host sync."""
-        assert self.test_cfg['seg']['mode'] in ['whole'] and not self.seg_head.align_corners
+        """inference_seg + argmax as ONE launch on the head's logits (ops.seg_predict; ops.seg_predict_slide on the logits of
+        all windows in test mode 'slide'): uint8 (B, Ho, Wo) on the device, no up-sampled tensor, no softmax (monotone), no
+        host sync."""
+        mode = self._seg_test_mode()
+        assert not self.seg_head.align_corners
         ori_shape = img_meta[0]['ori_shape']
         assert all(_['ori_shape'] == ori_shape for _ in img_meta)
-        neck_feature, backbone_feature = self.extract_feat(img)
-        seg_logit = self.seg_head.forward_test(neck_feature, backbone_feature, img_meta, self.shared_encoder)
         flip = None
         if img_meta[0].get('flip', False):
             flip = img_meta[0]['flip_direction']
             assert flip in ['horizontal', 'vertical']
+        if mode == 'slide':  # the windows' forward passes, then ONE launch (ops.seg_predict_slide) merges, rescales and arg-maxes
+            cfg = self.test_cfg['seg']
+            logits, _ = self.slide_window_logits(img, img_meta)
+            sized = dict(crop_hw=img_meta[0]['img_shape'][:2], out_hw=ori_shape[:2]) if rescale else {}
+            return ops.seg_predict_slide(logits, img.shape[0], img.shape[2:], cfg['crop_size'], cfg['stride'], flip=flip, **sized)
+        neck_feature, backbone_feature = self.extract_feat(img)
+        seg_logit = self.seg_head.forward_test(neck_feature, backbone_feature, img_meta, self.shared_encoder)
         if not rescale:
             return ops.seg_predict(seg_logit, img.shape[2:], flip=flip)
         return ops.seg_predict(seg_logit, img.shape[2:], crop_hw=img_meta[0]['img_shape'][:2], out_hw=ori_shape[:2], flip=flip)
@@ -295,7 +354,10 @@ class MTL(nn.Module):
                 seg_prob += self.inference_seg(img, meta, rescale)
             seg_prob /= len(imgs)
             return list(seg_prob.argmax(dim=1).cpu().numpy())
-        assert self.test_cfg['seg']['mode'] in ['whole'] and not self.seg_head.align_corners
+        if self._seg_test_mode() == 'slide':
+            raise NotImplementedError("aug_test_seg(on_device=True) with test_cfg['seg']['mode'] = 'slide': multi-scale / flip "
+                                      "testing of sliding-window inference runs on the host route only (on_device=False)")
+        assert not self.seg_head.align_corners
         ori_shape = img_metas[0][0]['ori_shape']
         assert all(_['ori_shape'] == ori_shape for meta in img_metas for _ in meta)
         logits, canvases, crops, flips = [], [], [], []

@@ -18,7 +18,8 @@ CPU tensor, or a non-zero return code raises.
     losses     box utilities, match_cost_batched, lsap_*, focal / box loss sums, upsample_ce, upsample_ce_weighted
     distutil   packed scalar all-reduces
     seg_eval   seg_predict (resample + flip + arg-max of the seg logits), seg_predict_tta (the same over V views: softmax, mean,
-               arg-max), seg_areas (mmseg pre_eval areas)
+               arg-max), slide_windows / seg_predict_slide (test mode 'slide': the windows' logits merged, rescaled and arg-maxed),
+               seg_areas (mmseg pre_eval areas)
     det_eval   det_decode (sigmoid + top-k + box decoding of a batch), det_match (COCOeval's per-image matching)
 
 Callers use `from rscotr_amd import ops; ops.linear(...)`: every public (and test-visible) name of the submodules is

@@ -1,6 +1,6 @@
 """Segmentation evaluation on the device: the inference tail of MTL.simple_test_seg (resample, flip, arg-max), that of
-MTL.aug_test_seg (the same over V views: softmax, mean, arg-max) and mmseg's pre_eval areas (intersect_and_union), one launch
-each (csrc/seg_eval.hip).  No op synchronises with the host."""
+MTL.aug_test_seg (the same over V views: softmax, mean, arg-max), that of test mode 'slide' (the windows' logits merged,
+rescaled, arg-maxed) and mmseg's pre_eval areas (intersect_and_union), one launch each (csrc/seg_eval.hip).  No op synchronises with the host."""
 import numpy as np
 import torch
 
@@ -28,6 +28,70 @@ def seg_predict(logit, canvas_hw, crop_hw=None, out_hw=None, flip=None):
     out = torch.empty((B, max(Ho, 0), max(Wo, 0)), dtype=torch.uint8, device=logit.device)
     lib.call('rscotr_seg_predict_u8', logit.data_ptr(), out.data_ptr(), B, C, h, w, H, W, int(rescale), hs, ws, Ho, Wo,
              _FLIP[flip], _stream())
+    return out
+
+
+def _pair(v, what):
+    v = tuple(int(a) for a in v) if isinstance(v, (tuple, list)) else (int(v), int(v))
+    if len(v) != 2:
+        raise ValueError(f'{what} is (y, x) or one integer, got {v!r}')
+    return v
+
+
+def slide_windows(H, W, crop_size, stride):
+    """The window grid of mmseg's EncoderDecoder.slide_inference on an (H, W) canvas -> [(y1, y2, x1, x2)] in visiting order
+    (row-major, y outer).  Per axis max(n - crop + stride - 1, 0) // stride + 1 windows, window i ending at
+    min(i * stride + crop, n) and starting max(end - crop, 0): the last one is shifted back inside the image, and an axis
+    shorter than the crop has one window, the whole axis.  ValueError: a non-positive size, or a stride larger than the crop
+    on an axis where the image exceeds the crop (pixels between two windows would be covered by none)."""
+    H, W = int(H), int(W)
+    (ch, cw), (sy, sx) = _pair(crop_size, 'crop_size'), _pair(stride, 'stride')
+    if min(H, W, ch, cw, sy, sx) <= 0:
+        raise ValueError(f'slide_windows: non-positive size (canvas {H} x {W}, crop_size {(ch, cw)}, stride {(sy, sx)})')
+    for n, crop, s, axis in ((H, ch, sy, 'y'), (W, cw, sx, 'x')):
+        if n > crop and s > crop:
+            raise ValueError(f'slide_windows: stride {s} larger than the crop {crop} on the {axis} axis ({n} pixels): '
+                             'pixels between two windows would be covered by none')
+
+    def axis(n, crop, s):
+        spans = []
+        for i in range(max(n - crop + s - 1, 0) // s + 1):
+            b = min(i * s + crop, n)
+            spans.append((max(b - crop, 0), b))
+        return spans
+    return [(y1, y2, x1, x2) for y1, y2 in axis(H, ch, sy) for x1, x2 in axis(W, cw, sx)]
+
+
+def seg_predict_slide(logits, batch, canvas_hw, crop_size, stride, crop_hw=None, out_hw=None, flip=None):
+    """The tail of test mode 'slide' as ONE launch.  logits (len(windows) * batch, C, h, w): the head's logits of every window
+    of slide_windows(*canvas_hw, crop_size, stride) in visiting order, the batch innermost.  -> uint8 label maps (batch, Ho, Wo):
+    arg-max over the channels of the canvas map (per pixel the in-order sum over the covering windows of the window's logits
+    resampled to the window size, bilinear, align_corners=False, divided by their number) and, when `out_hw` is given
+    (rescale), cropped to `crop_hw` (default: the canvas) and resampled to `out_hw`; without it the maps have the canvas
+    size.  flip: None | 'horizontal' | 'vertical', applied to the finished map.  See include/rscotr.h,
+    rscotr_seg_predict_slide_u8."""
+    if flip not in _FLIP:
+        raise ValueError(f"flip must be None, 'horizontal' or 'vertical', got {flip!r}")
+    H, W = (int(v) for v in canvas_hw)
+    (ch, cw), (sy, sx) = _pair(crop_size, 'crop_size'), _pair(stride, 'stride')
+    windows = slide_windows(H, W, (ch, cw), (sy, sx))
+    B = int(batch)
+    if B <= 0:
+        raise ValueError(f'seg_predict_slide: non-positive batch {B}')
+    if logits.dim() != 4 or logits.shape[0] != len(windows) * B:
+        raise ValueError(f'seg_predict_slide: logits {tuple(logits.shape)} are not (windows * batch, C, h, w) with '
+                         f'{len(windows)} windows x batch {B}')
+    rescale = out_hw is not None
+    if crop_hw is not None and not rescale:
+        raise ValueError('crop_hw needs out_hw (the crop belongs to the rescale stage)')
+    logits = _f32c(logits.detach())
+    _chk(logits)
+    _, C, h, w = logits.shape
+    hs, ws = (H, W) if crop_hw is None else (int(v) for v in crop_hw)
+    Ho, Wo = (int(v) for v in out_hw) if rescale else (H, W)
+    out = torch.empty((B, max(Ho, 0), max(Wo, 0)), dtype=torch.uint8, device=logits.device)
+    lib.call('rscotr_seg_predict_slide_u8', logits.data_ptr(), out.data_ptr(), B, C, h, w, H, W, ch, cw, sy, sx, int(rescale),
+             hs, ws, Ho, Wo, _FLIP[flip], _stream())
     return out
 
 
