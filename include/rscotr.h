@@ -31,7 +31,7 @@ extern "C" {
  * `stream` in the LayerNorm, window-attention, MSDA backward, pack4, splitk_flush and grouped-dW entries = revision 6;
  * round 6 = 7; 11 added the resampling input entries rscotr_img_aug_u8 / rscotr_seg_label_aug_u8; the
  * evaluation entries since — seg_predict / seg_areas, det_decode / det_match, seg_predict_tta, seg_predict_slide — are additive and change no
- * argument list, so they keep 11: a library without them fails to bind by name).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
+ * argument list, so they keep 11: a library without them fails to bind by name; the seg head's scheme-1 entries rscotr_seg_mix_* likewise).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
  * its first call (rscotr_amd/_lib.py does) — a stale .so would take a stream handle for a pointer. */
 #define RSCOTR_ABI_VERSION 11
 int rscotr_version(void);
@@ -598,6 +598,26 @@ int rscotr_level_embed_bwd(const float* g, float* dw, const int* sizes, int L, i
  * all-True reset to all-False -> out (rows, th*tw) bool (1 byte each, 1 = blocked). */
 int rscotr_seg_attn_mask(const float* mask_pred, unsigned char* out, int rows, int h, int w, int th, int tw,
                          void* stream);
+
+/* Class logits of the seg head's scheme 1 (models/multi/seg_head/mask2former_head.py:118-125, last prediction):
+ *   cls_pred = cls_embed(d) (B,Q,K), mask_pred = einsum('bqd,bdhw->bqhw', e, mask_feature), seg = einsum('bqc,bqhw->bchw')
+ * re-associated so that the (B,Q,h,w) mask logits are never formed:
+ *   mix[b,k,d] = sum_q cls[b,q,k] e[b,q,d]     seg[b,k,p] = sum_d mix[b,k,d] mf[b,p,d]
+ * cls (B,Q,K); e (B,Q,D); mf (B,P,D) = the mask features in token layout, P = h*w; mix (B,K,D) is written by _fwd and read
+ * by _bwd (the caller keeps it); seg (B,K,P).  1 <= K <= 32, D in {64, 128, 256}, Q >= 1, P >= 1, B <= 512; e, mf, mix, dmf
+ * 16-byte aligned.  _fwd: two launches (mix, then one pass over mf).
+ * _bwd, from g (B,K,P): dmf (B,P,D) = sum_k g mix; dmix[b,k,d] = sum_p g[b,k,p] mf[b,p,d] (scratch of B*K*D floats, written);
+ *   de (B,Q,D) = sum_k cls dmix; dcls (B,Q,K) = sum_d e dmix.  dmf, de, dcls may each be NULL (not wanted): without dmf the
+ *   pass over mf stores no gradient rows, without de and dcls it leaves no partial sums and the two small launches are skipped
+ *   (cls, e, dmix, workspace may then be NULL), and with all three NULL nothing is launched.  One pass over mf (dmf and the
+ *   per-workgroup partial dmix, in `workspace`), a fold of the partials in workgroup order, one launch for de and dcls.
+ * Fixed summation order throughout, no atomics: bit-reproducible.  workspace: rscotr_seg_mix_workspace() bytes, 16-byte aligned. */
+int64_t rscotr_seg_mix_workspace(void);
+int rscotr_seg_mix_fwd(const float* cls, const float* e, const float* mf, float* mix, float* seg, int B, int Q, int K, int D,
+                       int P, void* stream);
+int rscotr_seg_mix_bwd(const float* g, const float* cls, const float* e, const float* mf, const float* mix, float* dmf,
+                       float* de, float* dcls, float* dmix, int B, int Q, int K, int D, int P, float* workspace,
+                       int64_t workspace_bytes, void* stream);
 
 /* ---- detection loss arithmetic ---------------------------------------------------------------------------------
  * rscotr_match_cost: mmdet FocalLossCost + BBoxL1Cost(xywh) + IoUCost(giou) (HungarianAssigner.assign reached from

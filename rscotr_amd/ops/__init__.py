@@ -13,7 +13,7 @@ CPU tensor, or a non-zero return code raises.
     matmul     gemm / gemm_batched / colsum, linear / mlp
     norm       layer_norm, layer_norm_fork, group_norm_tokens
     deform     msda, msda_prep, msda_attention (mmcv MultiScaleDeformableAttention)
-    attention  swin_window_attention, mha (nn.MultiheadAttention), mask_logits, seg_attn_mask
+    attention  swin_window_attention, mha (nn.MultiheadAttention), mask_logits, seg_class_logits, seg_attn_mask
     glue       level_embed_add, fan_out, cdn_queries, sine_embed4, neck im2col, layout helpers, cls pooling / loss
     losses     box utilities, match_cost_batched, lsap_*, focal / box loss sums, upsample_ce, upsample_ce_weighted
     distutil   packed scalar all-reduces

@@ -1,5 +1,5 @@
 """Dense attention: the Swin window attention node, torch.nn.MultiheadAttention as one autograd node (`mha`), the mask
-logits of the seg decoder and its attention-mask kernel."""
+logits of the seg decoder, the class logits of its scheme 1 and its attention-mask kernel."""
 import torch
 from torch.autograd import Function
 
@@ -369,6 +369,78 @@ class _MaskLogits(Function):
 def mask_logits(e, mask_tokens):
     """e (B,Q,C) query embeddings, mask_tokens (B,h*w,C) mask features in token layout -> (B,Q,h*w)."""
     return _MaskLogits.apply(e, mask_tokens)
+
+
+# limits of rscotr_seg_mix_* (csrc/seg_mix.hip: SMX_*); a forward workgroup takes SEG_MIX_FWD_ROWS pixels of an image per trip, a
+# backward workgroup (512 // (D // 4)) * (2 if K <= 16 else 1), and the grids stop at SEG_MIX_FWD_WG / SEG_MIX_BWD_WG workgroups
+# over the whole batch
+SEG_MIX_MAX_K, SEG_MIX_DIMS, SEG_MIX_MAX_B = 32, (64, 128, 256), 512
+SEG_MIX_FWD_WG, SEG_MIX_FWD_ROWS, SEG_MIX_BWD_WG = 1024, 32, 512
+
+
+def seg_mix_bwd_rows(K, D):
+    return (512 // (D // 4)) * (2 if K <= 16 else 1)
+
+
+class _SegClassLogits(Function):
+    """seg[b, k, p] = sum_q cls[b, q, k] sum_d e[b, q, d] mf[b, p, d], re-associated through M = cls^T e (B,K,D): one pass
+    over mf per direction (rscotr_seg_mix_*), the (B,Q,P) mask logits never formed."""
+
+    @staticmethod
+    def forward(ctx, cls_pred, e, mf):
+        cls_pred, e, mf = _f32c(cls_pred), _f32c(e), _f32c(mf)
+        _chk(cls_pred, e, mf)
+        B, Q, K = cls_pred.shape
+        D, P = e.shape[2], mf.shape[1]
+        mix = torch.empty((B, K, D), dtype=torch.float32, device=mf.device)
+        out = torch.empty((B, K, P), dtype=torch.float32, device=mf.device)
+        with _Prof('seg_mix_fwd', 4 * B * P * (D + K)):
+            lib.call('rscotr_seg_mix_fwd', cls_pred.data_ptr(), e.data_ptr(), mf.data_ptr(), mix.data_ptr(), out.data_ptr(),
+                     B, Q, K, D, P, _stream())
+        ctx.save_for_backward(cls_pred, e, mf, mix)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        cls_pred, e, mf, mix = ctx.saved_tensors
+        B, Q, K = cls_pred.shape
+        D, P = e.shape[2], mf.shape[1]
+        need = ctx.needs_input_grad
+        if not any(need):
+            return None, None, None
+        g = _f32c(g)
+        dev = mf.device
+        dcls = torch.empty_like(cls_pred) if need[0] else None
+        de = torch.empty_like(e) if need[1] else None
+        dmf = torch.empty_like(mf) if need[2] else None  # (no pass-over-mf store and no 4 * B * P * D bytes when the mask features are frozen)
+        dmix = torch.empty_like(mix) if (need[0] or need[1]) else None
+        nws = lib.rscotr_seg_mix_workspace()
+        with _Prof('seg_mix_bwd', 4 * B * P * (D * (2 if need[2] else 1) + K)):
+            lib.call('rscotr_seg_mix_bwd', g.data_ptr(), cls_pred.data_ptr(), e.data_ptr(), mf.data_ptr(), mix.data_ptr(),
+                     _ptr(dmf), _ptr(de), _ptr(dcls), _ptr(dmix), B, Q, K, D, P, _WS.get(nws, dev).data_ptr(), nws, _stream())
+        return dcls, de, dmf
+
+
+def seg_class_logits(cls_pred, e, mask_tokens):
+    """Scheme 1 of Mask2FormerHead (mask2former_head.py:118-125): cls_pred (B,Q,K) class scores of the queries, e (B,Q,D) their
+    mask embeddings, mask_tokens (B,h*w,D) the mask features in token layout (the contiguous tensor the pixel decoder's last
+    Linear wrote) -> (B,K,h*w) = einsum('bqc,bqp->bcp', cls_pred, einsum('bqd,bpd->bqp', e, mask_tokens)), fp32, with all three
+    gradients.  1 <= K <= 32, D in (64, 128, 256), Q >= 1, h*w >= 1, 1 <= B <= 512: anything else is a ValueError."""
+    if cls_pred.dim() != 3 or e.dim() != 3 or mask_tokens.dim() != 3:
+        raise ValueError(f'seg_class_logits: cls_pred (B,Q,K), e (B,Q,D), mask_tokens (B,P,D) expected, got '
+                         f'{tuple(cls_pred.shape)}, {tuple(e.shape)}, {tuple(mask_tokens.shape)}')
+    B, Q, K = cls_pred.shape
+    D, P = e.shape[2], mask_tokens.shape[1]
+    if e.shape[:2] != (B, Q) or mask_tokens.shape[0] != B or mask_tokens.shape[2] != D:
+        raise ValueError(f'seg_class_logits: shapes disagree: cls_pred {tuple(cls_pred.shape)}, e {tuple(e.shape)}, '
+                         f'mask_tokens {tuple(mask_tokens.shape)}')
+    if not 1 <= K <= SEG_MIX_MAX_K:
+        raise ValueError(f'seg_class_logits: K = {K} class channels, the kernel takes 1 <= K <= {SEG_MIX_MAX_K}')
+    if D not in SEG_MIX_DIMS:
+        raise ValueError(f'seg_class_logits: D = {D} feature channels, the kernel takes D in {SEG_MIX_DIMS}')
+    if Q < 1 or P < 1 or not 1 <= B <= SEG_MIX_MAX_B or P >= 2 ** 31:
+        raise ValueError(f'seg_class_logits: Q = {Q}, P = {P}, B = {B}: Q >= 1, 1 <= P < 2^31 and 1 <= B <= {SEG_MIX_MAX_B} required')
+    return _SegClassLogits.apply(cls_pred, e, mask_tokens)
 
 
 def seg_attn_mask(mask_pred, target_size, heads):

@@ -159,7 +159,9 @@ class Mask2FormerHead(nn.Module):
                  loss_decode=dict(type='CrossEntropyLoss', use_sigmoid=False, loss_weight=1.0), align_corners=False,
                  init_cfg=None, sampler=None):
         super().__init__()
-        assert scheme == 2, 'the MTL configs use scheme=2 (queries are the output channels)'
+        if scheme not in (1, 2):
+            raise NotImplementedError(f'Mask2FormerHead: scheme={scheme!r} (1: class logits mixed from the queries, 2: the queries are '
+                                      'the output channels)')
         assert not align_corners
         self.scheme, self.num_classes, self.num_queries = scheme, num_classes, num_queries
         self.align_corners, self.ignore_index = align_corners, ignore_index
@@ -178,6 +180,8 @@ class Mask2FormerHead(nn.Module):
         self.query_embed = nn.Embedding(num_queries, feat_channels)
         self.query_feat = nn.Embedding(num_queries, feat_channels)
         self.level_embed = nn.Embedding(num_transformer_feat_level, feat_channels)
+        if scheme == 1:  # mask2former_head.py:78-79 (num_classes + 1 channels; init_weights leaves it at nn.Linear's default)
+            self.cls_embed = nn.Linear(feat_channels, num_classes + 1)
         self.mask_embed = nn.Sequential(
             nn.Linear(feat_channels, feat_channels), nn.ReLU(inplace=True),
             nn.Linear(feat_channels, feat_channels), nn.ReLU(inplace=True),
@@ -214,6 +218,20 @@ class Mask2FormerHead(nn.Module):
         mask_pred = ops.mask_logits(e, mask_feature.permute(0, 2, 3, 1).reshape(B_, h_ * w_, C_)).view(B_, -1, h_, w_)
         attn_mask = ops.seg_attn_mask(mask_pred, attn_mask_target_size, self.num_heads)
         return mask_pred, attn_mask
+
+    def forward_class_logits(self, decoder_out, mask_feature):
+        """Scheme 1, the last prediction (mask2former_head.py:118-125): decoder_out (B,Q,C) -> seg logits (B,K,h,w),
+        K = num_classes + 1.  einsum('bqc,bqhw->bchw', cls_pred, mask_pred) without mask_pred: ops.seg_class_logits mixes the mask
+        embeddings into K rows first and passes over the mask features once.  No attention mask either: nothing reads it."""
+        pn = self.transformer_decoder.post_norm
+        d = ops.layer_norm(decoder_out, pn.weight, pn.bias)
+        m = self.mask_embed
+        e = ops.mlp(d, [(m[0].weight, m[0].bias), (m[2].weight, m[2].bias), (m[4].weight, m[4].bias)], act='relu', range_out=False)
+        cls_pred = ops.linear(d, self.cls_embed.weight, self.cls_embed.bias, range_out=False)
+        B_, C_, h_, w_ = mask_feature.shape
+        # (the channels-last map is a view of the pixel decoder's token tensor: flattening it back is free)
+        seg = ops.seg_class_logits(cls_pred, e, mask_feature.permute(0, 2, 3, 1).reshape(B_, h_ * w_, C_))
+        return seg.view(B_, -1, h_, w_)
 
     def forward(self, encoder, neck_feats, backbone_feats, img_metas, record=None):
         B = len(img_metas)
@@ -253,6 +271,8 @@ class Mask2FormerHead(nn.Module):
                                query_sum=q_sum, key_sum=key_sums[li], next_query_pos=nxt)
             if nxt is not None:
                 query_feat, q_sum = query_feat
+            if self.scheme == 1 and nxt is None:
+                return self.forward_class_logits(query_feat, mask_features)
             mask_pred, attn_mask = self.forward_head(
                 query_feat, mask_features, memorys[(i + 1) % self.num_transformer_feat_level].shape[-2:])
         return mask_pred  # only the last prediction is supervised (mask2former_head.py:199)
