@@ -31,7 +31,8 @@ extern "C" {
  * `stream` in the LayerNorm, window-attention, MSDA backward, pack4, splitk_flush and grouped-dW entries = revision 6;
  * round 6 = 7; 11 added the resampling input entries rscotr_img_aug_u8 / rscotr_seg_label_aug_u8; the
  * evaluation entries since — seg_predict / seg_areas, det_decode / det_match, seg_predict_tta, seg_predict_slide — are additive and change no
- * argument list, so they keep 11: a library without them fails to bind by name; the seg head's scheme-1 entries rscotr_seg_mix_* likewise).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
+ * argument list, so they keep 11: a library without them fails to bind by name; the seg head's scheme-1 entries rscotr_seg_mix_* and
+ * the det input chain rscotr_img_aug_chain_u8 likewise).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
  * its first call (rscotr_amd/_lib.py does) — a stale .so would take a stream handle for a pointer. */
 #define RSCOTR_ABI_VERSION 11
 int rscotr_version(void);
@@ -748,6 +749,22 @@ int rscotr_img_aug_u8(const uint8_t* src, const int64_t* meta, const int32_t* ta
                       int B, int Hout, int Wout, const float* mean3, const float* std3, int to_rgb, void* stream);
 int rscotr_seg_label_aug_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, int64_t* out, int B, int Hout,
                             int Wout, int reduce_zero_label, int pad_val, void* stream);
+
+/* rscotr_img_aug_chain_u8: flip -> resize -> crop -> resize of a det batch in ONE launch, the frame between the two resizes never
+ * stored: mmdet RandomFlip + AutoAugment([Resize], [Resize, RandomCrop, Resize(override=True)]) + Normalize + Pad of the
+ * reference's configs/det/dino_4scale_r50_1x1_50e_dior.py:110-155.  meta: device (B, 20) int64 rows of rscotr_img_aug_u8's
+ * layout, read as {byte offset, H, W, row stride in bytes, frame-1 window w, h, 0, stage-1 x-table offset, y-table offset,
+ * x taps K, y taps K, stage-1 resample mode (0 nearest | 1 bilinear), stage-2 x-table offset, stage-2 y-table offset, out w,
+ * out h, reserved x 4}.  Stage-1 entries are rscotr_img_aug_u8's and describe the crop window of frame 1 (entry j = window
+ * coordinate j; a flip in front of the first resize is mirrored into the x entries by the host: the kernel flips nothing).
+ * Stage-2 entries have 4 words {first window coordinate of frame 1, taps n <= 2, w0, w1} (OpenCV fixed-point bilinear of the
+ * window, 11-bit weights; the final window's offset folded in; one tap of weight 2048 = read as is, which is how a sample with
+ * one resize rides in the same launch).  out = clamp((sum wy * sum wx * f1 + 2^21) >> 22) with every f1 the uint8 pixel stage 1
+ * gives, so the batch is bit-equal to resampling into a uint8 frame, cropping it and resampling that.  No photometric stage, no
+ * erasing.  Every stage-1 index must lie inside its source, every stage-2 index inside the frame-1 window, out w / h <= Wout /
+ * Hout (caller-checked: the entry cannot read device memory). */
+int rscotr_img_aug_chain_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, float* out, int B, int Hout,
+                            int Wout, const float* mean3, const float* std3, int to_rgb, void* stream);
 
 /* ---- RandAugment on the device ---------------------------------------------------------------------------------------------
  * Replaces mmcls RandAugment(policies=rand_increasing_policies, num_policies=2, total_level=10, magnitude_level=9,

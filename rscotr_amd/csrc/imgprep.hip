@@ -345,6 +345,54 @@ __global__ __launch_bounds__(256) void img_frames_kernel(const uint8_t* __restri
   o[2] = (uint8_t)u[2];
 }
 
+// ---- flip -> resize -> crop -> resize in one launch (rscotr_img_aug_chain_u8) ------------------------------------------------------
+// mmdet's AutoAugment policy of the DETR recipe (Resize, RandomCrop, Resize(override)): the frame between the two resizes is a
+// uint8 image on the CPU path; here it is never stored.  An output pixel reads its <= 2 x 2 pixels of frame 1 through the
+// stage-2 entries (cv2 bilinear; coordinates of the crop window of frame 1), and each of them is made by resample_u8 through
+// the stage-1 entries, rounded and clamped to uint8 as the stored frame would be; the stage-2 blend is the same fixed-point
+// form.  So the result is bit-equal to the two passes, at <= 16 byte-triplet reads and 12 B written per output pixel.  The meta
+// row is rscotr_img_aug_u8's: words 0 .. 11 describe stage 1 (out w / h = the crop window of frame 1, flip 0: an early flip is
+// in the x entries), words 12 .. 15 = stage-2 x-table offset, y-table offset (entries of 4 words), final out w, out h.  A
+// sample with one stage carries identity stage-2 entries (one tap of weight 2048).
+__global__ __launch_bounds__(256) void img_aug_chain_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
+                                                            const int32_t* __restrict__ tables, float* __restrict__ out,
+                                                            int Hout, int Wout, PrepNorm nm, int to_rgb) {
+  const int b = blockIdx.z, y = blockIdx.y;
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= Wout) return;
+  const int64_t* m = meta + (long)b * IMGAUG_META;
+  float v[3] = {0.f, 0.f, 0.f};  // mmcv Pad runs after Normalize with pad_val = 0
+  if (y < (int)m[15] && x < (int)m[14]) {
+    const int32_t* tx = tables + m[12] + (long)x * 4;
+    const int32_t* ty = tables + m[13] + (long)y * 4;
+    const int nx = tx[1], ny = ty[1];
+    int acc[3] = {0, 0, 0};
+    for (int a = 0; a < ny; ++a) {
+      int hs[3] = {0, 0, 0};
+      for (int t = 0; t < nx; ++t) {
+        int u[3];
+        resample_u8(src, m, tables, tx[0] + t, ty[0] + a, u);
+        const int w = tx[2 + t];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) hs[c] += w * u[c];
+      }
+      const int wy = ty[2 + a];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[c] += wy * hs[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int u = min(max((acc[to_rgb ? 2 - c : c] + (1 << 21)) >> 22, 0), 255);
+      v[c] = ((float)u - nm.mean[c]) * nm.inv_std[c];
+    }
+  }
+  const long plane = (long)Hout * Wout;
+  float* o = out + (long)b * 3 * plane + (long)y * Wout + x;
+  o[0] = v[0];
+  o[plane] = v[1];
+  o[2 * plane] = v[2];
+}
+
 extern "C" int rscotr_img_aug_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, const float* params,
                                  float* out, int B, int Hout, int Wout, const float* mean3, const float* std3, int to_rgb,
                                  void* stream) {
@@ -361,6 +409,23 @@ extern "C" int rscotr_img_aug_u8(const uint8_t* src, const int64_t* meta, const 
   img_aug_kernel<<<dim3((Wout + 255) / 256, Hout, B), 256, 0, (hipStream_t)stream>>>(src, meta, tables, params, out, Hout,
                                                                                    Wout, nm, to_rgb ? 1 : 0);
   return check_launch("rscotr_img_aug_u8");
+}
+
+extern "C" int rscotr_img_aug_chain_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, float* out, int B,
+                                       int Hout, int Wout, const float* mean3, const float* std3, int to_rgb, void* stream) {
+  if (int e = check_prep("rscotr_img_aug_chain_u8", src, meta, out, B, Hout, Wout)) return e;
+  if (B && Hout && Wout && !tables) return fail(RSCOTR_E_ARG, "rscotr_img_aug_chain_u8: null pointer");
+  if (!mean3 || !std3) return fail(RSCOTR_E_ARG, "rscotr_img_aug_chain_u8: mean / std (3 host floats each) required");
+  PrepNorm nm;
+  for (int c = 0; c < 3; ++c) {
+    if (!(std3[c] > 0.f)) return fail(RSCOTR_E_ARG, "rscotr_img_aug_chain_u8: std[%d] must be positive", c);
+    nm.mean[c] = mean3[c];
+    nm.inv_std[c] = (float)(1.0 / (double)std3[c]);  // as rscotr_img_prep_u8
+  }
+  if (B == 0 || Hout == 0 || Wout == 0) return RSCOTR_OK;
+  img_aug_chain_kernel<<<dim3((Wout + 255) / 256, Hout, B), 256, 0, (hipStream_t)stream>>>(src, meta, tables, out, Hout, Wout,
+                                                                                         nm, to_rgb ? 1 : 0);
+  return check_launch("rscotr_img_aug_chain_u8");
 }
 
 extern "C" int rscotr_seg_label_aug_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, int64_t* out, int B,

@@ -10,7 +10,8 @@ Everything from the crop window on runs on the device; the host only draws the r
 
     resample   the integer resampling tables the host builds (cv2 bilinear, Pillow bicubic, nearest), cv2's bicubic remap weights
     randaug    RandAugment's configuration, draws, meta rows and warp tables
-    collate    DeviceCollate (one host plan under three launch routes), the dataset configs' settings, the seg TTA collate
+    autoaug    multi-scale Resize and mmdet AutoAugment (Resize / RandomCrop policies): draws, box chain, chain-launch tables
+    collate    DeviceCollate (one host plan under four launch routes), the dataset configs' settings, the seg TTA collate
     config     build_collate: an mm* pipeline config -> a collate
     datasets   FolderClsDataset, CocoDetDataset, TileSegDataset with their evaluate / pre_eval, DeviceLoader"""
 from .collate import (AUG_META, AUG_PARAMS, CLS_ERASING, IMG_NORM, PHOTOMETRIC, PM_BRIGHT, PM_CONTRAST, PM_CONTRAST_FIRST, PM_HUE,

@@ -7,7 +7,9 @@ a seeded run makes the same decisions, and sends the raw bytes with the launches
   plain      every optional stage off: `rscotr_img_prep_u8` (+ `rscotr_seg_label_prep_u8`), crop / flip / normalize / pad;
   tables     `resize=`, `random_resized_crop=`, `photometric=`, `random_erasing=`: `rscotr_img_aug_u8` (+ `rscotr_seg_label_aug_u8`)
              over the per-axis tables of resample.py;
-  RandAugment `rand_augment=` (cls): `rscotr_img_frames_u8` -> `rscotr_randaug_u8` per slot -> `rscotr_img_aug_u8` (randaug.py)."""
+  RandAugment `rand_augment=` (cls): `rscotr_img_frames_u8` -> `rscotr_randaug_u8` per slot -> `rscotr_img_aug_u8` (randaug.py);
+  chain      `auto_augment=` (det), when a sample of the batch drew a policy with two Resizes: `rscotr_img_aug_chain_u8`, both
+             resamplings in one launch (autoaug.py); a batch of one-Resize samples is the table route's."""
 import ctypes
 import math
 import random
@@ -18,9 +20,10 @@ import torch
 
 from .. import ops
 from .._lib import lib
+from .autoaug import aa_boxes, aa_config, aa_draw, aa_geometry, chain_tables, check_resize, resize_shape
 from .randaug import RA_STATS, _ra_config, ra_draws, ra_slot_rows
 from .resample import (RESAMPLE_LINEAR, RESAMPLE_NEAREST, RESAMPLE_PIL, _axis_nearest, _AxisTables, _round_up, cubic_weight_table,
-                       rescale_size, scale_boxes)
+                       scale_boxes)
 
 IMG_NORM = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
 META = 10  # include/rscotr.h: rscotr_img_prep_u8's meta row
@@ -41,7 +44,8 @@ def _aug_row(off, shape, stride, d, geo, pm=None, erase=None, patch_off=0):
     """One rscotr_img_aug_u8 meta row (include/rscotr.h): a source of `shape` at byte offset `off`, the window and flip of the
     draw `d`, the tables `geo` (`_AxisTables.add_window`), the photometric draws and the erasing draws with their patch's offset."""
     (_, _, cw, ch), (mode, xt, kx, yt, ky) = d['win'], geo
-    row = [off, shape[0], shape[1], stride, cw, ch, int(d['flip']), xt, yt, kx, ky, mode] + [0] * (AUG_META - 12)
+    flip = int(d['flip'] and not d.get('flip_first', False))  # (a flip in front of the geometry is in the x entries)
+    row = [off, shape[0], shape[1], stride, cw, ch, flip, xt, yt, kx, ky, mode] + [0] * (AUG_META - 12)
     if pm is not None:
         row[12], row[13] = pm[0], pm[4]
     if erase is not None:
@@ -60,9 +64,10 @@ class DeviceCollate:
     def __init__(self, task, device, img_norm_cfg=None, flip_prob=0.5, size_divisor=None, crop_size=None,
                  cat_max_ratio=1.0, reduce_zero_label=False, seg_pad_val=255, ignore_index=255, resize=None,
                  random_resized_crop=None, photometric=None, random_erasing=None, resize_backend='cv2',
-                 rand_augment=None, labels=True):
+                 rand_augment=None, labels=True, auto_augment=None):
         """Optional stages (None = off; any of them on routes the batch through `rscotr_img_aug_u8`):
-        resize: mmseg / mmdet Resize, dict(img_scale=(long, short), ratio_range=None | (lo, hi), keep_ratio=True), or
+        resize: mmseg / mmdet Resize, dict(img_scale=(long, short), ratio_range=None | (lo, hi), keep_ratio=True), or with
+                img_scale=[(long, short), ...] and multiscale_mode='value' | 'range' (a scale drawn per sample), or
                 mmcls Resize, dict(size=(h, w)) (a fixed size);
         random_resized_crop: mmcls RandomResizedCrop, dict(size, scale, ratio, max_attempts) (RANDOM_RESIZED_CROP);
         photometric: mmseg PhotoMetricDistortion, True or dict (PHOTOMETRIC);
@@ -71,7 +76,10 @@ class DeviceCollate:
         rand_augment: mmcls RandAugment (task 'cls' only), True (RAND_AUGMENT, the reference's settings) or dict(policies,
                 num_policies, magnitude_level, total_level=30, magnitude_std=0., hparams); it routes the batch through
                 `rscotr_img_frames_u8` -> `rscotr_randaug_u8` per slot -> `rscotr_img_aug_u8`;
-        labels: False = a seg batch without `gt_semantic_seg` (test time: the label maps are neither staged nor resampled)."""
+        labels: False = a seg batch without `gt_semantic_seg` (test time: the label maps are neither staged nor resampled);
+        auto_augment: mmdet AutoAugment (task 'det' only), dict(policies=[[Resize | RandomCrop dicts]]) (autoaug.py): RandomFlip
+                is drawn and applied FIRST, then one policy per sample; a sample whose policy resizes twice sends the batch
+                through `rscotr_img_aug_chain_u8`.  It is the whole geometry: no other optional stage goes with it."""
         assert task in ('cls', 'det', 'seg')
         self.task, self.device = task, torch.device(device)
         cfg = dict(IMG_NORM if img_norm_cfg is None else img_norm_cfg)
@@ -86,6 +94,8 @@ class DeviceCollate:
         self.resize = None if resize is None else dict(dict(ratio_range=None, keep_ratio=True), **resize)
         if self.resize is not None and ('size' in self.resize) == ('img_scale' in self.resize):
             raise ValueError('resize takes img_scale=(long, short) (mmseg / mmdet) or size=(h, w) (mmcls)')
+        if self.resize is not None and 'img_scale' in self.resize:
+            check_resize(self.resize)
         self.rrc = None if random_resized_crop is None else dict(RANDOM_RESIZED_CROP, **random_resized_crop)
         self.photometric = None if not photometric else dict(PHOTOMETRIC, **(photometric if isinstance(photometric, dict)
                                                                              else {}))
@@ -95,8 +105,19 @@ class DeviceCollate:
             raise ValueError("rand_augment is for task 'cls' only: boxes and label maps do not follow its warps")
         self.rand_augment = None if rand_augment is None or rand_augment is False else _ra_config(rand_augment)
         self._ra_wtab = None  # device copy of cubic_weight_table() (uploaded once)
+        self.auto_augment = None
+        if auto_augment is not None:
+            if task != 'det':
+                raise ValueError("auto_augment is for task 'det' only")
+            for name, v in (('Resize', self.resize), ('RandomResizedCrop', self.rrc), ('PhotoMetricDistortion', self.photometric),
+                            ('RandomErasing', self.erasing), ('RandAugment', self.rand_augment), ('RandomCrop', crop_size)):
+                if v is not None:
+                    raise NotImplementedError(f'{name} together with AutoAugment')
+            if resize_backend != 'cv2':
+                raise NotImplementedError(f'AutoAugment with resize_backend={resize_backend!r}: a chain resamples cv2 bilinear')
+            self.auto_augment = aa_config(auto_augment)
         self.augmented = any(x is not None for x in (self.resize, self.rrc, self.photometric, self.erasing,
-                                                     self.rand_augment))
+                                                     self.rand_augment, self.auto_augment))
         self.skipped = []  # transforms build_collate was told to skip
         self.labels = bool(labels)
         self._stage = None  # pinned byte staging buffer (grow-only)
@@ -150,18 +171,8 @@ class DeviceCollate:
         return (H - th) // 2, (W - tw) // 2, th, tw
 
     def _resize_shape(self, H, W, rng):
-        """mmseg / mmdet Resize (random_sample_ratio, then mmcv rescale_size) or mmcls Resize -> (new_w, new_h)."""
-        r = self.resize
-        if 'size' in r:
-            return int(r['size'][1]), int(r['size'][0])
-        scale = tuple(r['img_scale'])
-        if r['ratio_range'] is not None:
-            lo, hi = r['ratio_range']
-            ratio = rng.random_sample() * (hi - lo) + lo
-            scale = int(scale[0] * ratio), int(scale[1] * ratio)
-        if r['keep_ratio']:
-            return rescale_size(W, H, scale)[0]
-        return int(scale[0]), int(scale[1])
+        """mmseg / mmdet Resize (its scale draw, then mmcv rescale_size) or mmcls Resize -> (new_w, new_h)."""
+        return resize_shape(self.resize, H, W, rng)
 
     def _photometric_draws(self, rng):
         """mmseg PhotoMetricDistortion.__call__'s draws -> (flags, beta, contrast alpha, saturation alpha, hue delta)."""
@@ -218,8 +229,14 @@ class DeviceCollate:
         erasing): a dict with the source rectangle `src` (x, y, w, h), the resized frame `rsz` (w, h), the window `win`
         (x0, y0, w, h) in that frame, `flip`, `pm` (photometric draws or None), `ra` (the RandAugment plan, `ra_draws`; absent
         when the stage is off) and `erase` (or None).  `py_rng`: the Python-side generator of RandAugment (default `random`).
-        With every optional stage off these are the window and flip draws of the plain route."""
+        With every optional stage off these are the window and flip draws of the plain route.  With `auto_augment` the flip is
+        drawn first and applies to the source (`flip_first`), `steps` is the drawn policy's walk (`aa_draw`) and `chain` is None or
+        the second stage, dict(win1: the crop window of frame `rsz`, rsz2: the frame `win` lies in) (`aa_geometry`)."""
         H, W = img_shape[:2]
+        if self.auto_augment is not None:  # mmdet RandomFlip, then AutoAugment: one policy's Resize / RandomCrop draws
+            flip = bool(rng.rand() < self.flip_prob)
+            policy, steps = aa_draw(self.auto_augment, H, W, rng)
+            return dict(aa_geometry(H, W, steps), flip=flip, flip_first=True, policy=policy, steps=steps, pm=None, erase=None)
         if self.rrc is not None:
             oy, ox, th, tw = self._rrc_params(H, W, rng)
             size = self.rrc['size']
@@ -279,6 +296,8 @@ class DeviceCollate:
             if resized:
                 m['scale_factor'] = np.array([rw / sw, rh / sh, rw / sw, rh / sh], dtype=np.float32)
                 m['keep_ratio'] = bool(self.resize is not None and self.resize.get('keep_ratio') and 'size' not in self.resize)
+            if d.get('scale_factor') is not None:  # AutoAugment: the LAST Resize of the drawn policy
+                m['scale_factor'], m['keep_ratio'] = d['scale_factor'], d['keep_ratio']
             if self.rand_augment is not None:
                 m['rand_augment'] = d['ra']  # the plan that was applied (`ra_draws`)
             metas.append(m)
@@ -301,12 +320,15 @@ class DeviceCollate:
             boxes, labels, hboxes, hlabels = [], [], [], []
             for s, d, m in zip(samples, p.ds, batch['img_metas']):
                 hb = np.asarray(s['gt_bboxes'], dtype=np.float32).reshape(-1, 4)
+                hl = np.asarray(s['gt_labels'], dtype=np.int64).reshape(-1)
+                if self.auto_augment is not None:  # flip, then the policy's scale / shift / clip / drop chain
+                    hb, hl = aa_boxes(hb, hl, s['img'].shape[1], d['flip'], d['steps'])
                 if p.resized:
                     hb = scale_boxes(hb, m['scale_factor'], m['img_shape'])
                 cw = d['win'][2]
-                if d['flip']:  # mmdet RandomFlip.bbox_flip, horizontal (on the host: the boxes are a few dozen floats)
+                if d['flip'] and self.auto_augment is None:
+                    # mmdet RandomFlip.bbox_flip, horizontal (on the host: the boxes are a few dozen floats)
                     hb = np.stack([np.float32(cw) - hb[:, 2], hb[:, 1], np.float32(cw) - hb[:, 0], hb[:, 3]], -1)
-                hl = np.asarray(s['gt_labels'], dtype=np.int64).reshape(-1)
                 boxes.append(torch.from_numpy(np.ascontiguousarray(hb)).to(self.device))
                 labels.append(torch.from_numpy(np.ascontiguousarray(hl)).to(self.device))
                 hboxes.append(np.ascontiguousarray(hb))
@@ -383,7 +405,9 @@ class DeviceCollate:
         erasing patches | tables | params | meta | label meta."""
         B = len(p.imgs)
         tabs = _AxisTables()
-        geo = [tabs.add_window(self.resample, d, p.Hout, p.Wout) for d in p.ds]
+        geo = [tabs.add_window(self.resample, d, p.Hout, p.Wout,
+                               mirror_w=a.shape[1] if d['flip'] and d.get('flip_first', False) else None)
+               for a, d in zip(p.imgs, p.ds)]
         lgeo = [tabs.add_window(RESAMPLE_NEAREST, d, p.Hout, p.Wout) for _, d in zip(p.segs, p.ds)]
         tabs.check([a.shape for a in p.imgs])  # (the label tables are the nearest form of the same geometry on the same shapes)
         patches = [d['erase'][4] for d in p.ds if d['erase'] is not None]
@@ -404,6 +428,23 @@ class DeviceCollate:
         p_tab, p_prm, p_meta, p_lmeta = [ptr + o for o in offs[-4:]]
         self._launch_img('rscotr_img_aug_u8', (ptr, p_meta, p_tab, p_prm), p)
         self._launch_labels('rscotr_seg_label_aug_u8', (ptr, p_lmeta, p_tab), p)
+
+    def _launch_chain(self, p):
+        """The det batch of AutoAugment in which a sample resizes twice: `rscotr_img_aug_chain_u8`, every sample in the one
+        launch (a one-Resize sample with identity stage-2 entries).  Layout of the one upload: images | tables | meta."""
+        B = len(p.imgs)
+        tabs = _AxisTables()
+        meta = np.zeros((max(B, 1), AUG_META), np.int64)
+        arrays = p.imgs + [None, meta]
+        geo = [chain_tables(tabs, d, a.shape, p.Hout, p.Wout) for a, d in zip(p.imgs, p.ds)]
+        arrays[-2] = tabs.flat()
+        offs = self._upload_offsets(arrays)
+        for b, (src, d, (mode, xt, kx, yt, ky, x2, y2, cw, ch)) in enumerate(zip(p.imgs, p.ds, geo)):
+            meta[b, :16] = [offs[b], src.shape[0], src.shape[1], src.shape[1] * 3, cw, ch, 0, xt, yt, kx, ky, mode, x2, y2,
+                            d['win'][2], d['win'][3]]
+        buf, offs = self._upload(arrays)
+        ptr = buf.data_ptr()
+        self._launch_img('rscotr_img_aug_chain_u8', (ptr, ptr + offs[-1], ptr + offs[-2]), p)
 
     def _launch_randaug(self, p):
         """The cls batch with RandAugment: frames -> one `rscotr_randaug_u8` per slot -> `rscotr_img_aug_u8` over identity
@@ -452,6 +493,8 @@ class DeviceCollate:
         p = self._plan(samples, rng or np.random, py_rng or random)
         if self.rand_augment is not None:
             self._launch_randaug(p)
+        elif any(d.get('chain') for d in p.ds):
+            self._launch_chain(p)
         elif self.augmented:
             self._launch_tables(p)
         else:

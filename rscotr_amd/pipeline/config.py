@@ -10,7 +10,9 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
     """Map an mm* pipeline (a list of transform dicts, as in the dataset configs) to a DeviceCollate.
 
     Understood: LoadImageFromFile, LoadAnnotations (reduce_zero_label), Resize (mmseg / mmdet img_scale + ratio_range +
-    keep_ratio; mmcls size + backend + interpolation), RandomResizedCrop, RandomCrop, RandomFlip, PhotoMetricDistortion,
+    keep_ratio, for 'det' and 'seg' also a list of scales + multiscale_mode 'value' | 'range'; mmcls size + backend +
+    interpolation), AutoAugment for task 'det' (policies of Resize and mmdet RandomCrop(crop_type, allow_negative_crop=True)
+    behind a RandomFlip: the DETR multi-scale recipe), RandomResizedCrop, RandomCrop, RandomFlip, PhotoMetricDistortion,
     RandomErasing, Normalize, Pad, ImageToTensor, ToTensor, DefaultFormatBundle, Collect, MultiScaleFlipAug (its single
     scale and its transforms; flip=False — for task 'seg' also flip=True, `img_ratios` and several scales, up to
     SEG_TTA_MAX_VIEWS views: the result is then a SegTTACollate) and RandAugment when `policies` is a non-empty list of the 13 implemented types
@@ -62,11 +64,16 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
                     return
                 if sc is None:  # MultiScaleFlipAug(img_scale=None, img_ratios=[1.0]): the image's own size
                     return
+                multi = {}
                 if isinstance(sc, list):
-                    if len(sc) != 1:
+                    if len(sc) == 1:
+                        sc = sc[0]
+                    elif task not in ('det', 'seg'):
                         raise NotImplementedError('Resize with several img_scale values')
-                    sc = sc[0]
-                kw['resize'] = dict(img_scale=tuple(sc), ratio_range=t.get('ratio_range'), keep_ratio=t.get('keep_ratio', True))
+                    else:  # a scale drawn per sample (mmseg / mmdet Resize.random_select / random_sample)
+                        sc, multi = [tuple(v) for v in sc], dict(multiscale_mode=t.get('multiscale_mode', 'range'))
+                kw['resize'] = dict(img_scale=sc if multi else tuple(sc), ratio_range=t.get('ratio_range'),
+                                    keep_ratio=t.get('keep_ratio', True), **multi)
             kw['resize_backend'] = _backend(t)
         elif typ == 'RandomResizedCrop':
             kw['random_resized_crop'] = {k: t[k] for k in ('size', 'scale', 'ratio', 'max_attempts') if k in t}
@@ -76,8 +83,25 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
             kw['crop_size'] = (cs, cs) if isinstance(cs, int) else tuple(cs)
             kw['cat_max_ratio'] = t.get('cat_max_ratio', 1.0)
             kw['ignore_index'] = t.get('ignore_index', 255)
+        elif typ == 'AutoAugment' and task == 'det':
+            policies = []
+            for k, pol in enumerate(t['policies']):
+                steps = []
+                for u in pol:
+                    if u.get('type') in ('Resize', 'RandomCrop'):
+                        steps.append(dict(u))
+                    elif unsupported == 'skip':
+                        skipped.append(u.get('type'))
+                    else:
+                        raise NotImplementedError(f"AutoAugment policy {k}: {u.get('type')} is not implemented by the device "
+                                                  "collate (a policy holds Resize and RandomCrop only; build_collate(..., "
+                                                  "unsupported='skip') leaves it out)")
+                policies.append(steps)
+            kw['auto_augment'] = dict(policies=policies)
         elif typ == 'RandomFlip' and tta is not None:
             pass  # (MultiScaleFlipAug sets the flip of every view)
+        elif typ == 'RandomFlip' and 'auto_augment' in kw:
+            raise NotImplementedError('RandomFlip after AutoAugment (the chain flips the source in front of its geometry)')
         elif typ == 'RandomFlip':
             kw['flip_prob'] = t.get('flip_prob', t.get('flip_ratio', t.get('prob', 0.0))) or 0.0
         elif typ == 'PhotoMetricDistortion':
@@ -100,6 +124,12 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
                                       f"unsupported='skip') leaves it out)")
     for t in pipeline_cfg:
         visit(t)
+    if 'auto_augment' in kw:  # (it is the whole geometry of its batch, and its launches carry no colour stage)
+        for name, key in (('Resize', 'resize'), ('RandomResizedCrop', 'random_resized_crop'), ('RandomCrop', 'crop_size'),
+                          ('PhotoMetricDistortion', 'photometric'), ('RandomErasing', 'random_erasing'),
+                          ('RandAugment', 'rand_augment')):
+            if key in kw:
+                raise NotImplementedError(f'{name} together with AutoAugment')
     if tta is not None:
         kw.pop('flip_prob')
         col = SegTTACollate(device, tta, resize=kw.pop('tta_resize', None), img_norm_cfg=norm, **kw)

@@ -76,6 +76,18 @@ def _axis_pil_bicubic(n_in, n_out, src0, o0, count):
     return _table(xmin + src0, xmax, w)
 
 
+def mirror_x(t, W):
+    """The x entries of a row of width W that is flipped left-right BEFORE it is resampled: taps first .. first + n - 1 of the
+    flipped row are taps W - first - n .. W - first - 1 of the stored one, with the weights in reverse order (<= 2 taps)."""
+    assert t.shape[1] <= 4
+    t = t.copy()
+    t[:, 0] = W - t[:, 0] - t[:, 1]
+    if t.shape[1] == 4:
+        two = t[:, 1] == 2
+        t[two, 2:4] = t[two, 2:4][:, ::-1]
+    return t
+
+
 _AXIS = {RESAMPLE_NEAREST: _axis_nearest, RESAMPLE_LINEAR: _axis_linear, RESAMPLE_PIL: _axis_pil_bicubic}
 
 
@@ -91,13 +103,17 @@ class _AxisTables:
         self.size += t.size
         return self.size - t.size, t.shape[1] - 2
 
-    def add_window(self, mode, d, Hout, Wout):
+    def add_window(self, mode, d, Hout, Wout, mirror_w=None):
         """The x and y tables of one sample's draw `d` (DeviceCollate.draw): identity nearest entries where it is not resized
-        (its window is read as is) -> (mode, x offset, x taps, y offset, y taps)."""
+        (its window is read as is) -> (mode, x offset, x taps, y offset, y taps).  `mirror_w`: the source, that many pixels
+        wide, is flipped left-right in front of the resampling (`mirror_x`)."""
         (sx, sy, sw, sh), (rw, rh), (x0, y0, cw, ch) = d['src'], d['rsz'], d['win']
         assert 0 <= x0 and 0 <= y0 and x0 + cw <= rw and y0 + ch <= rh and cw <= Wout and ch <= Hout
         mode = RESAMPLE_NEAREST if (sw, sh) == (rw, rh) else mode
-        xt, kx = self.add(_AXIS[mode](sw, rw, sx, x0, cw))
+        tx = _AXIS[mode](sw, rw, sx, x0, cw)
+        if mirror_w is not None:
+            tx = mirror_x(tx, mirror_w)
+        xt, kx = self.add(tx)
         yt, ky = self.add(_AXIS[mode](sh, rh, sy, y0, ch))
         return mode, xt, kx, yt, ky
 
