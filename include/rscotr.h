@@ -32,7 +32,7 @@ extern "C" {
  * round 6 = 7; 11 added the resampling input entries rscotr_img_aug_u8 / rscotr_seg_label_aug_u8; the
  * evaluation entries since — seg_predict / seg_areas, det_decode / det_match, seg_predict_tta, seg_predict_slide — are additive and change no
  * argument list, so they keep 11: a library without them fails to bind by name; the seg head's scheme-1 entries rscotr_seg_mix_* and
- * the det input chain rscotr_img_aug_chain_u8 likewise).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
+ * the det input chain rscotr_img_aug_chain_u8 likewise, and the Dice seg loss rscotr_upsample_dice_*).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
  * its first call (rscotr_amd/_lib.py does) — a stale .so would take a stream handle for a pointer. */
 #define RSCOTR_ABI_VERSION 11
 int rscotr_version(void);
@@ -541,6 +541,28 @@ int rscotr_upsample_ce_ohem(const int64_t* label, const float* class_weight, con
                             float* workspace, int64_t workspace_bytes, void* stream);
 int rscotr_upsample_ce_w_bwd(const float* logit, const int64_t* label, const float* lse, const float* pix_weight,
                              const float* grad_scale, float* dlogit, int B, int C, int h, int w, int H, int W,
+                             int ignore_index, void* stream);
+
+/* ---- fused bilinear upsample + softmax + Dice (seg loss; additive entries: the ABI revision is unchanged) ------------------
+ * mmseg 0.28 DiceLoss as BaseDecodeHead.losses reaches it, without the up-sampled logits or the probabilities in memory:
+ *   p = softmax(resize(logit, (H,W), bilinear, align_corners=False), dim=1);  t = one-hot of clamp(label, 0, C-1);
+ *   v = [label != ignore_index];  num[b,c] = 2 sum_pix p t v + smooth;  den[b,c] = sum_pix (p^2 + t) + smooth (not masked);
+ *   loss[0] = loss_weight / C * sum_{c != ignore_index} class_weight[c] * mean_b (1 - num / den).
+ *   logit (B,C,h,w); label (B,H,W) int64 (clamped before it selects a channel: never an index); class_weight C floats or NULL;
+ *   H * W <= 2^24 (the label counts are exact float sums), else RSCOTR_E_SHAPE.
+ *   _fwd writes lse (B,H,W), the per-pixel log-sum-exp, coef (B,C,2) = {a, bcoef} = {-2k / den, 2k num / den^2} with
+ *     k = loss_weight * class_weight[c] / (C * B) (0 for channel ignore_index), and loss[0]: two launches, per-workgroup partial rows
+ *     in `workspace` (rscotr_upsample_dice_workspace(B, C) bytes) folded in fixed order, no atomics: bit-reproducible.
+ *   _bwd: dlogit (B,C,h,w) = grad_scale[0] * d(loss)/d(logit), grad_scale a DEVICE scalar: a per-pixel launch writes
+ *     pix_s (B,H,W) = sum_c (a t v + bcoef p_c) p_c (the caller's scratch), then the gather of rscotr_upsample_ce_bwd with
+ *     p_c (a t v + bcoef p_c - pix_s) per pixel and class; cells no output pixel touches are written as exact zeros.
+ * No entry synchronises with the host or allocates: all of them can be captured in a hipGraph. */
+int64_t rscotr_upsample_dice_workspace(int B, int C);
+int rscotr_upsample_dice_fwd(const float* logit, const int64_t* label, const float* class_weight, float* lse, float* coef,
+                             float* loss, int B, int C, int h, int w, int H, int W, int ignore_index, float smooth,
+                             float loss_weight, float* workspace, int64_t workspace_bytes, void* stream);
+int rscotr_upsample_dice_bwd(const float* logit, const int64_t* label, const float* lse, const float* coef,
+                             const float* grad_scale, float* pix_s, float* dlogit, int B, int C, int h, int w, int H, int W,
                              int ignore_index, void* stream);
 
 /* Query position embedding of the DINO decoder (models/multi/bbox_head/transformer.py:43-76): pos (rows,4) = (x,y,w,h)

@@ -10,26 +10,10 @@
 // log-sum-exp per pixel (for backward) and three scalars; backward is a GATHER per low-resolution
 // cell (no atomics): lane = class, loop over the <= (2*sy)x(2*sx) output pixels the cell touches.
 //
-// PyTorch's upsample_bilinear2d (align_corners=False) source index: s = max((d + 0.5) * in/out - 0.5, 0),
-// i0 = floor(s), i1 = min(i0 + 1, in - 1), lambda1 = s - i0.
-#include "common.h"
+// The resize's source index (src_index) and the gather's block geometry are in seg_upsample.h, shared with csrc/seg_dice.hip.
+#include "seg_upsample.h"
 
 namespace rscotr {
-
-struct Interp {
-  int i0, i1;
-  float l0, l1;
-};
-
-__device__ __forceinline__ Interp src_index(int d, float scale, int in) {
-  Interp r;
-  const float s = fmaxf(((float)d + 0.5f) * scale - 0.5f, 0.f);
-  r.i0 = min((int)s, in - 1);
-  r.i1 = min(r.i0 + 1, in - 1);
-  r.l1 = s - (float)r.i0;
-  r.l0 = 1.f - r.l1;
-  return r;
-}
 
 // one thread per output pixel; classes streamed (online log-sum-exp + running arg-max)
 // WT (class weights / pixel sampling, rscotr_upsample_ce_w_fwd): the pixel's CE is also written to `nll` (0 for an ignored pixel)
@@ -117,9 +101,7 @@ __global__ __launch_bounds__(256) void upsample_ce_sums_kernel(const float* __re
 // pair) in registers and folds them into its private LDS column when the column pair changes (every ~8 pixels); the
 // (UCE_TB + 2)^2 cell neighbourhood of all classes, the labels and log-sum-exps of the footprint and the row / column
 // interpolation tables are staged in LDS once.  The four groups meet in fixed order: no atomics, bit-reproducible.
-constexpr int UCE_TB = 4;    // cells per block edge
-constexpr int UCE_NB = UCE_TB + 2;
-constexpr int UCE_FP = 48;   // staged footprint rows / columns (40 at x8); larger footprints read labels / lse from global memory
+// (UCE_TB, UCE_NB = UCE_TB + 2 and UCE_FP, the staged footprint edge: seg_upsample.h)
 
 // WT (rscotr_upsample_ce_w_bwd): every pixel's softmax - one-hot is multiplied by pixw[p] (class weight x sampling mask); a
 // pixel of weight 0 is staged as ignored.  The weights of a staged footprint take UCE_FP^2 more floats of LDS (80 KB in all:

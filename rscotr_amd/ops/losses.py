@@ -1,5 +1,5 @@
 """Detection / segmentation loss pieces: box utilities, matching cost, the assignment solvers, focal / box loss sums, the
-fused upsample + cross-entropy (plain, and with class weights / avg_non_ignore / OHEM)."""
+fused upsample + cross-entropy (plain, and with class weights / avg_non_ignore / OHEM), the fused upsample + Dice."""
 import math
 
 import torch
@@ -320,6 +320,62 @@ def upsample_ce_weighted(seg_logit, label, ignore_index=255, class_weight=None, 
     loss, sums, pix_weight = _UpsampleCEWeighted.apply(seg_logit, label, ignore_index, class_weight, norm, sel)
     acc = (sums[1] * 100.0 / (sums[2] + torch.finfo(torch.float32).eps)).reshape(1)
     return loss, acc, pix_weight
+
+
+class _UpsampleDice(Function):
+    """The fused bilinear upsample + softmax + Dice loss (rscotr_upsample_dice_*).  Forward leaves the per-pixel log-sum-exp and
+    the two backward coefficients of every (image, class); the upstream gradient meets them on the device (grad_scale)."""
+
+    @staticmethod
+    def forward(ctx, logit, label, ignore_index, smooth, class_weight, loss_weight):
+        logit = _f32c(logit)
+        label = label.contiguous()
+        cw = None if class_weight is None else _f32c(class_weight)
+        _chk(logit, label, cw)
+        B, C, h, w = logit.shape
+        H, W = label.shape[-2:]
+        if cw is not None and cw.numel() != C:
+            raise ValueError(f'class_weight has {cw.numel()} entries, the logits have {C} channels')
+        dev = logit.device
+        lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        coef = torch.empty((B, C, 2), dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        nws = lib.rscotr_upsample_dice_workspace(B, C)
+        # the logits twice (log-sum-exp, then the sums), labels, lse written and re-read
+        with _Prof('upsample_dice_fwd', 8 * B * C * h * w + 16 * B * H * W):
+            lib.call('rscotr_upsample_dice_fwd', logit.data_ptr(), label.data_ptr(), _ptr(cw), lse.data_ptr(), coef.data_ptr(),
+                     loss.data_ptr(), B, C, h, w, H, W, int(ignore_index), float(smooth), float(loss_weight),
+                     _WS.get(nws, dev).data_ptr(), nws, _stream())
+        ctx.save_for_backward(logit, label, lse, coef)
+        ctx.ignore = int(ignore_index)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        logit, label, lse, coef = ctx.saved_tensors
+        B, C, h, w = logit.shape
+        H, W = label.shape[-2:]
+        gscale = g_loss.reshape(1).float().contiguous()
+        pix_s = torch.empty_like(lse)
+        dlogit = torch.empty_like(logit)
+        # pre-pass: logits, labels, lse read, S written; gather: logits read, gradient written, labels, lse, S read
+        with _Prof('upsample_dice_bwd', 12 * B * C * h * w + 32 * B * H * W):
+            lib.call('rscotr_upsample_dice_bwd', logit.data_ptr(), label.data_ptr(), lse.data_ptr(), coef.data_ptr(),
+                     gscale.data_ptr(), pix_s.data_ptr(), dlogit.data_ptr(), B, C, h, w, H, W, ctx.ignore, _stream())
+        return dlogit, None, None, None, None, None
+
+
+def upsample_dice(seg_logit, label, ignore_index=255, smooth=1.0, class_weight=None, loss_weight=1.0):
+    """mmseg 0.28 DiceLoss (exponent 2) as BaseDecodeHead.losses reaches it, fused: bilinear resize (align_corners=False) to the
+    label size, softmax, and per (image, class)
+        num = 2 * sum p t v + smooth,  den = sum (p^2 + t) + smooth,
+    t the one-hot of clamp(label, 0, C-1), v = [label != ignore_index] (den is not masked: mmseg's quirk);
+        loss = loss_weight / C * sum_{c != ignore_index} class_weight[c] * mean_b (1 - num / den).
+    Neither the up-sampled logits nor the probabilities are materialised (rscotr_upsample_dice_*); bit-reproducible.
+    seg_logit (B,C,h,w), label (B,H,W) int64, class_weight a float tensor / list of C entries or None -> loss 0-d."""
+    if class_weight is not None and not torch.is_tensor(class_weight):
+        class_weight = torch.as_tensor(class_weight, dtype=torch.float32, device=seg_logit.device)
+    return _UpsampleDice.apply(seg_logit, label, ignore_index, smooth, class_weight, loss_weight)
 
 
 class _DetProposals(Function):

@@ -27,16 +27,7 @@ class CrossEntropyLoss(nn.Module):
             raise NotImplementedError('CrossEntropyLoss: use_sigmoid / use_mask are not implemented (softmax CE only)')
         if reduction not in ('mean', 'sum'):
             raise NotImplementedError(f"CrossEntropyLoss: reduction={reduction!r} (only 'mean' and 'sum')")
-        if isinstance(class_weight, str):
-            if not class_weight.endswith('.npy'):
-                raise ValueError(f'class_weight file {class_weight!r}: only .npy is read')
-            import numpy as np
-            class_weight = np.load(class_weight).astype('float64').reshape(-1).tolist()
-        elif isinstance(class_weight, (list, tuple)):
-            class_weight = [float(v) for v in class_weight]
-        elif class_weight is not None:
-            raise TypeError(f'class_weight must be a list / tuple of floats or a .npy path, got {type(class_weight).__name__}')
-        self.reduction, self.class_weight, self.avg_non_ignore = reduction, class_weight, bool(avg_non_ignore)
+        self.reduction, self.class_weight, self.avg_non_ignore = reduction, _class_weight_list(class_weight), bool(avg_non_ignore)
         self.loss_weight, self.loss_name = loss_weight, loss_name
         self._cw = {}  # device -> tensor (not a buffer: the state dict keeps the reference's keys)
 
@@ -45,14 +36,63 @@ class CrossEntropyLoss(nn.Module):
         return self.class_weight is None and not self.avg_non_ignore and self.reduction == 'mean'
 
     def weight_on(self, device, num_channels):
-        if self.class_weight is None:
-            return None
-        if len(self.class_weight) != num_channels:
-            raise ValueError(f'class_weight has {len(self.class_weight)} entries, the logits have {num_channels} channels')
-        t = self._cw.get(str(device))
-        if t is None:
-            t = self._cw[str(device)] = torch.tensor(self.class_weight, dtype=torch.float32, device=device)
-        return t
+        return _class_weight_on(self, device, num_channels)
+
+
+def _class_weight_list(class_weight):
+    """mmseg get_class_weight: None, a list / tuple of floats, or the path of a .npy file -> None or a list of floats."""
+    if isinstance(class_weight, str):
+        if not class_weight.endswith('.npy'):
+            raise ValueError(f'class_weight file {class_weight!r}: only .npy is read')
+        import numpy as np
+        return np.load(class_weight).astype('float64').reshape(-1).tolist()
+    if isinstance(class_weight, (list, tuple)):
+        return [float(v) for v in class_weight]
+    if class_weight is not None:
+        raise TypeError(f'class_weight must be a list / tuple of floats or a .npy path, got {type(class_weight).__name__}')
+    return None
+
+
+def _class_weight_on(loss, device, num_channels):
+    """The loss module's class weights as a tensor on `device` (cached per device), checked against the logit channels."""
+    if loss.class_weight is None:
+        return None
+    if len(loss.class_weight) != num_channels:
+        raise ValueError(f'class_weight has {len(loss.class_weight)} entries, the logits have {num_channels} channels')
+    t = loss._cw.get(str(device))
+    if t is None:
+        t = loss._cw[str(device)] = torch.tensor(loss.class_weight, dtype=torch.float32, device=device)
+    return t
+
+
+@MODELS.register_module()
+class DiceLoss(nn.Module):
+    """mmseg 0.28 DiceLoss as the seg head uses it: the options are stored here and applied by the fused kernels
+    (ops.upsample_dice).  As in mmseg, forward swallows the `weight` and `ignore_index` that BaseDecodeHead.losses passes: a
+    pixel sampler's mask and the head's ignore_index do not reach this loss; its OWN ignore_index masks the numerator and
+    skips that channel.  reduction / avg_factor act on a scalar: 'mean', 'sum' and 'none' are the same loss.  No parameters,
+    no buffers: the state dict keeps the reference's keys."""
+
+    def __init__(self, smooth=1, exponent=2, reduction='mean', class_weight=None, loss_weight=1.0, ignore_index=255,
+                 loss_name='loss_dice'):
+        super().__init__()
+        if exponent != 2:
+            raise NotImplementedError(f'DiceLoss: exponent={exponent!r} (the fused kernels implement exponent 2)')
+        if reduction not in ('mean', 'sum', 'none'):
+            raise ValueError(f"DiceLoss: reduction={reduction!r} (one of 'mean', 'sum', 'none')")
+        self.smooth, self.exponent, self.reduction = float(smooth), 2, reduction
+        self.class_weight = _class_weight_list(class_weight)
+        self.loss_weight, self.ignore_index, self.loss_name = float(loss_weight), int(ignore_index), loss_name
+        self._cw = {}
+
+    def weight_on(self, device, num_channels):
+        return _class_weight_on(self, device, num_channels)
+
+    def forward(self, seg_logit, label, **kwargs):
+        """seg_logit (B,C,h,w) at the head's resolution, label (B,H,W) int64 -> loss_weight * dice (0-d)."""
+        cw = self.weight_on(seg_logit.device, seg_logit.shape[1])
+        return ops.upsample_dice(seg_logit, label, self.ignore_index, smooth=self.smooth, class_weight=cw,
+                                 loss_weight=self.loss_weight)
 
 
 @MODELS.register_module()
@@ -187,11 +227,19 @@ class Mask2FormerHead(nn.Module):
             nn.Linear(feat_channels, feat_channels), nn.ReLU(inplace=True),
             nn.Linear(feat_channels, out_channels))
         # a dict or a list of dicts, as mmseg's BaseDecodeHead takes it (mask2former_head.py:85-93); no parameters, no keys
-        cfgs = list(loss_decode) if isinstance(loss_decode, (list, tuple)) else [loss_decode]
+        # The single-dict form stays what it was, one CrossEntropyLoss; a DiceLoss is an entry of a loss_decode LIST (next to a
+        # CrossEntropyLoss entry as in mmseg's documented pair, or on its own: [dict(type='DiceLoss')])
+        is_list = isinstance(loss_decode, (list, tuple))
+        cfgs = list(loss_decode) if is_list else [loss_decode]
+        allowed = ('CrossEntropyLoss', 'DiceLoss') if is_list else ('CrossEntropyLoss',)
         for c in cfgs:
-            if not isinstance(c, dict) or c.get('type') != 'CrossEntropyLoss':
+            if not isinstance(c, dict) or c.get('type') not in allowed:
                 name = c.get('type') if isinstance(c, dict) else type(c).__name__
-                raise NotImplementedError(f'loss_decode type {name!r}: the fused seg loss implements CrossEntropyLoss only')
+                if name == 'DiceLoss':
+                    raise NotImplementedError("loss_decode type 'DiceLoss' as a single dict: DiceLoss is taken as an entry of a "
+                                              "loss_decode list, e.g. [dict(type='CrossEntropyLoss'), dict(type='DiceLoss')]")
+                raise NotImplementedError(f'loss_decode type {name!r}: the fused seg losses implement CrossEntropyLoss, and DiceLoss '
+                                          'as an entry of a list, only')
         built = [MODELS.build(c) for c in cfgs]
         self.loss_decode = nn.ModuleList(built) if isinstance(loss_decode, (list, tuple)) else built[0]
         self.sampler = None
@@ -283,6 +331,25 @@ class Mask2FormerHead(nn.Module):
 
     def losses(self, seg_logit, seg_label):
         entries = list(self.loss_decode) if isinstance(self.loss_decode, nn.ModuleList) else [self.loss_decode]
+        ce = [ld for ld in entries if isinstance(ld, CrossEntropyLoss)]
+        if len(ce) == len(entries):
+            return self._ce_losses(ce, seg_logit, seg_label)
+        # a list with DiceLoss entries: the cross-entropy entries take the path they take alone; every Dice entry is one fused
+        # call (the sampler's mask and the head's ignore_index do not reach it, as in mmseg); entries of one name add up
+        out = self._ce_losses(ce, seg_logit, seg_label) if ce else {}
+        acc_seg = out.pop('acc_seg', None)
+        label = seg_label.squeeze(1)
+        for ld in entries:
+            if isinstance(ld, DiceLoss):
+                loss = ld(seg_logit, label)
+                out[ld.loss_name] = out[ld.loss_name] + loss if ld.loss_name in out else loss
+        if acc_seg is None:  # no cross-entropy entry: mmseg reports the accuracy all the same
+            with torch.no_grad():
+                _, acc_seg = ops.upsample_ce(seg_logit.detach(), label, self.ignore_index)
+        out['acc_seg'] = acc_seg
+        return out
+
+    def _ce_losses(self, entries, seg_logit, seg_label):
         if self.sampler is None and len(entries) == 1 and entries[0].is_default:
             loss, acc = ops.upsample_ce(seg_logit, seg_label.squeeze(1), self.ignore_index)
             return {entries[0].loss_name: loss * entries[0].loss_weight, 'acc_seg': acc}
