@@ -20,6 +20,9 @@
 // fixed head; the products run on the matrix cores (see the section header below).  Backward
 // recomputes the probabilities from q, k (nothing but qkv is saved) and leaves the bias-table and
 // pad-token (qkv-bias) gradients as one partial row per workgroup, folded by a second launch.
+// In backward a workgroup that runs several items loads the operand tiles of the next item into
+// registers before the products of the current one, and every result leaves through an LDS tile as
+// 16-byte row pieces (see "Item loop of the backward" below).
 #include "common.h"
 #include "rscotr.h"
 
@@ -121,13 +124,30 @@ __device__ __forceinline__ float half_sum(float v) {
 // Four wavefronts per (window, head) item.  One wavefront per item is a chain of ~280 dependent-latency MFMAs,
 // five LDS phases and a 49-step row softmax: ~50 us per item however few items there are (stages 3-4 have 600 items for
 // 1024 SIMDs).  Here the 256 threads of a workgroup share one item: each wavefront stages one of the four operand tiles,
-// owns one 32 x 32 tile of S, the softmax runs four lanes per row, and the backward products are spread as
-//   waves 0,1: dP rows 0-31 / 32-63 (kept in registers) -> dS for those rows -> dQ rows 0-31 / 32-63
-//   waves 2,3: dV rows 0-31 / 32-63                                          -> dK rows 0-31 / 32-63
-// so the MFMA chain of an item is 16 + 32 + 25 instead of 278 issues.  The relative-position-bias gradient is a GATHER
+// owns one 32 x 32 tile of S, the softmax runs four lanes per row, the forward's O = P V runs on waves 0,1 (rows 0-31 /
+// 32-63), and the backward products are spread as
+//   waves 0,1: dP rows 0-31 / 32-63 (kept in registers) -> dS for those rows          -> dQ rows 0-31 / 32-63
+//   waves 2,3: dV rows 0-31 / 32-63 (registers) -> through sV to global memory while 0,1 form dS -> dK rows 0-31 / 32-63
+// so the MFMA chain of an item is 16 + 32 + 25 instead of 278 issues (dP + dV are 114 tile steps: an even four-way split
+// would be 29 against these 32, so that phase is left as it is).  The relative-position-bias gradient is a GATHER
 // (thread t < 169 sums dS over the <= 49 (i, j) pairs of its table entry in fixed order, in a register across the items
-// of the workgroup) instead of ~64 LDS float atomics per lane and item, and the pad-token (qkv-bias) sums are per-lane
-// registers folded wave by wave at the end: no atomics at all, bit-reproducible.
+// of the workgroup) instead of ~64 LDS float atomics per lane and item: no atomics at all, bit-reproducible.
+//
+// Item loop of the backward.  (1) Prefetch: the token map of item n + 1 is written (third of three sTok / sLab slots, so the row stores of
+// item n - 1 may still be reading theirs) and its operand tiles are loaded into registers (TileRegs) BEFORE the products of
+// item n; they go to LDS at the end of the iteration, once the last product has read the old tiles.  The wait for them
+// (wait_loads) stands BEFORE the last rows of item n are stored, so it covers the prefetch alone and those stores are not
+// waited for until the end of item n + 1.  GUARD: the map and the loads of item n + 1 sit
+// behind `more = bw + stride < B * nW` and nowhere else; the last item of a workgroup prefetches nothing, so no address is
+// formed from an item index >= B * nW.  The staged tiles cost 28 + 8 registers; with the per-thread address arithmetic
+// kept inside the loop (item_tid) the kernel still needs only 123 VGPRs and no scratch.
+// (2) Results: dV / dQ / dK go from the accumulators to an LDS tile ([49][33]: the operand tiles that are dead by then,
+// dV and dQ -> sV, dK -> sG) and from there to global memory as float4 pieces, eight lanes per token row like tile_load,
+// with one pad / real decision per piece from sTok and max|.| for the range word folded in the same pass.  The pad-token
+// (qkv-bias) sums are taken from the accumulators on their way to the tile (acc_to_tile; sPadm = the pad bits of the
+// token map), per lane and in register order, and folded wave by wave at the end.  Every product and every sum keeps the
+// order it had when each accumulator register was stored by its own instruction: the results are bit-identical to that
+// form (which a training run, where rounding differences grow from step to step, can be compared against).
 __device__ __forceinline__ void mma_rr1(f32x16& acc, const float* A, const float* B, int mi, int ni, int lane) {
   const int fr = lane & 31, fk = lane >> 5;
   const float* a = A + min(mi * 32 + fr, WN - 1) * LDT + fk;
@@ -196,7 +216,27 @@ __device__ __forceinline__ void softmax_rows4(float* sP, int tid) {
   }
 }
 
-// wave w stages operand tile w of the item (0: q * scale, 1: k, 2: v, 3: dO when `dout` is given)
+// wave w loads operand tile w of item (image b, token map sTok) into registers (0: q, 1: k, 2: v, 3: dO when `dout` is given)
+__device__ __forceinline__ void stage_load(TileRegs& r, const float* __restrict__ qkv, const float* __restrict__ qkv_b,
+                                           const float* __restrict__ dout, const WinGeom& g, int b, int head,
+                                           const int* sTok, int w, int lane) {
+  if (w == 3 && !dout) return;
+  const long L = (long)g.H * g.W;
+  const float* src = w == 3 ? dout + (long)b * L * g.C + head * HD : qkv + (long)b * L * 3 * g.C + head * HD + w * g.C;
+  const long tstride = w == 3 ? g.C : 3 * g.C;
+  const float* padv = (w == 3 || !qkv_b) ? nullptr : qkv_b + w * g.C + head * HD;
+  tile_load(r, src, tstride, padv, sTok, lane);
+}
+
+// ... and writes it to its LDS tile (q scaled)
+__device__ __forceinline__ void stage_store(const TileRegs& r, float* sQ, float* sK, float* sV, float* sG, float scale,
+                                            int w, int lane) {
+  if (w == 3 && !sG) return;
+  float* dst = w == 0 ? sQ : (w == 1 ? sK : (w == 2 ? sV : sG));
+  tile_store(r, dst, w == 0 ? scale : 1.f, lane);
+}
+
+// wave w stages operand tile w of the item at once (the forward's loop; 0: q * scale, 1: k, 2: v)
 __device__ __forceinline__ void stage_item_tiles(float* sQ, float* sK, float* sV, float* sG, const float* base,
                                                  const float* __restrict__ qkv_b, const float* dout_b, const WinGeom& g,
                                                  int head, const int* sTok, float scale, int w, int lane) {
@@ -210,11 +250,75 @@ __device__ __forceinline__ void stage_item_tiles(float* sQ, float* sK, float* sV
   tile_store(r, dst, w == 0 ? scale : 1.f, lane);
 }
 
+// Thread index as the item loop sees it: opaque to the optimiser, so that the per-thread address arithmetic of an item
+// (LDS tile offsets, row-piece indices, operand rows) is redone per item instead of being hoisted out of the loop and held
+// in registers across it: hoisted, the backward needs > 256 VGPRs and spills; inside the loop it needs ~125, no scratch.
+__device__ __forceinline__ int item_tid() {
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return t;
+}
+
+// every vector-memory operation of this wavefront has completed (vmcnt(0); the other counters are left alone).  Stated on
+// every path, where the compiler's own wait would sit inside the branch of the loading wavefronts only and a second one
+// would follow on the merged path, behind the row stores.
+__device__ __forceinline__ void wait_loads() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
+// token map of item bw (threads 0..48, all in wave 0): sTok = token index inside the image or -1 for a pad token,
+// sLab = shift-mask label; padm[0..1] = bit t of the 64-bit word: token t is a pad token
+__device__ __forceinline__ void token_map(const WinGeom& g, int bw, int* sLab, int* sTok, unsigned* padm, int tid) {
+  if (tid >= 64) return;
+  const int win = bw % g.nW;
+  const TokPos me = win_token(g, win / g.nWw, win % g.nWw, min(tid, WN - 1));
+  const unsigned long long pads = __ballot(tid < WN && me.pad);
+  if (tid < WN) {
+    sLab[tid] = me.label;
+    sTok[tid] = me.pad ? -1 : (int)me.tok;
+  }
+  if (tid == 0) {
+    padm[0] = (unsigned)pads;
+    padm[1] = (unsigned)(pads >> 32);
+  }
+}
+
+// accumulator of a 32-row tile (rows mi * 32 + crow, column lane & 31) -> result tile sO[49][LDT]; the rows of pad tokens
+// (bits of `pads`) are also added to `pad_acc`, element by element in register order: the summation order of the pad-token
+// (qkv-bias) gradient is that of the accumulator layout, item after item
+__device__ __forceinline__ void acc_to_tile(const f32x16& acc, float* sO, float scale, int mi, int lane,
+                                            unsigned long long pads, float& pad_acc) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int i = mi * 32 + crow(r, lane);
+    if (i < WN) {
+      sO[i * LDT + (lane & 31)] = acc[r] * scale;
+      if ((pads >> i) & 1ull) pad_acc += acc[r] * scale;
+    }
+  }
+}
+
+// rows of a result tile -> global memory: piece idx (< 49 * 8) is channels 4 (idx & 7) .. + 3 of token row idx >> 3;
+// dst_tok0 = channel 0 of token 0 of this head in the image.  Pad rows are skipped.  Returns max |.| of what was stored.
+__device__ __forceinline__ float tile_row_piece(const float* sO, float* __restrict__ dst_tok0, long tok_stride,
+                                                const int* sTok, int idx, float amx) {
+  const int t = idx >> 3, c4 = idx & 7;
+  const int tok = sTok[t];
+  if (tok >= 0) {
+    const float* s = sO + t * LDT + c4 * 4;
+    const float4 v = make_float4(s[0], s[1], s[2], s[3]);
+    *reinterpret_cast<float4*>(dst_tok0 + (long)tok * tok_stride + c4 * 4) = v;
+    amx = fmaxf(fmaxf(amx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+  }
+  return amx;
+}
+
 __global__ __launch_bounds__(256) void swin_wattn_fwd_mfma4_kernel(const float* __restrict__ qkv,
                                                                    const float* __restrict__ qkv_b,
                                                                    const float* __restrict__ table,
                                                                    float* __restrict__ out, WinGeom g, int B,
                                                                    unsigned* __restrict__ amax_out) {
+  // The forward keeps the plain loop (map, gather, products, per-register stores): with O = P V on the two wavefronts whose
+  // summation order the results are defined by, the prefetched loop and the LDS row stores of the backward measured 1-3 us
+  // SLOWER here at stages 1-2 and level at stages 3-4 (profiles/README.md); this kernel already runs four workgroups per CU.
   __shared__ float sQ[WN * LDT], sK[WN * LDT], sV[WN * LDT];
   __shared__ float sP[NPD * LDP];
   __shared__ float sT[TBL];
@@ -264,6 +368,22 @@ __global__ __launch_bounds__(256) void swin_wattn_fwd_mfma4_kernel(const float* 
   amax_commit(amax_out, amx);
 }
 
+// rows of the forward output for delta (four lanes per row, 8 channels each); zeros for pad rows and without `outp`
+__device__ __forceinline__ void delta_rows_load(float4& o_a, float4& o_b, const float* __restrict__ outp, const WinGeom& g,
+                                                int b, int head, const int* sTok, int tid) {
+  o_a = make_float4(0.f, 0.f, 0.f, 0.f);
+  o_b = o_a;
+  if (outp && (tid >> 2) < WN) {
+    const int tok = sTok[tid >> 2];
+    if (tok >= 0) {
+      const float4* o4 =
+          reinterpret_cast<const float4*>(outp + ((long)b * g.H * g.W + tok) * g.C + head * HD + (tid & 3) * 8);
+      o_a = o4[0];
+      o_b = o4[1];
+    }
+  }
+}
+
 __device__ __forceinline__ void swin_wattn_bwd_mfma4_body(const float* __restrict__ qkv,
                                                                    const float* __restrict__ qkv_b,
                                                                    const float* __restrict__ table,
@@ -274,49 +394,58 @@ __device__ __forceinline__ void swin_wattn_bwd_mfma4_body(const float* __restric
   __shared__ float sQ[WN * LDT], sK[WN * LDT], sV[WN * LDT], sG[WN * LDT];
   __shared__ float sP[NPD * LDP];
   __shared__ float sT[TBL];
-  __shared__ float sBw[4][3 * HD];
   float amx = 0.f;  // max |dqkv| of what this lane stores -> the gradient's range word (common.h: amax_commit)
   __shared__ float sDelta[64];
-  __shared__ int sLab[WN], sTok[WN];
+  __shared__ int sLab[3][WN], sTok[3][WN];
+  __shared__ unsigned sPadm[3][2];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 31;
   const int head = blockIdx.x % g.heads;
   const int stride = gridDim.x / g.heads;
+  const int nitem = B * g.nW;
   const float scale = 0.17677669529663687f;
   const long L = (long)g.H * g.W;
-  for (int t = tid; t < TBL; t += 256) sT[t] = table[t * g.heads + head];
-  for (int t = tid; t < NPD * LDP; t += 256) sP[t] = 0.f;
-  float dT = 0.f;                        // thread t < 169: gradient of table entry t over this workgroup's items
-  float accB[3] = {0.f, 0.f, 0.f};       // pad-token sums of this lane's rows: dq (waves 0,1), dk, dv (waves 2,3), column fr
+  float* prow = part + (long)blockIdx.x * WATTN_PROW;
+  int bw = blockIdx.x / g.heads;
+  float dT = 0.f;    // thread t < 169: gradient of table entry t over this workgroup's items
+  float accB[3] = {0.f, 0.f, 0.f};  // pad-token sums of this lane's rows: dq (waves 0,1), dk, dv (waves 2,3), column fr
+  if (bw < nitem) {  // (always with wattn_grid)
+    for (int t = tid; t < TBL; t += 256) sT[t] = table[t * g.heads + head];
+    for (int t = tid; t < NPD * LDP; t += 256) sP[t] = 0.f;
+    token_map(g, bw, sLab[0], sTok[0], sPadm[0], tid);
+    __syncthreads();
+  }
   const int tdy = tid / 13 - 6, tdx = tid % 13 - 6;
   const int iy0 = max(0, tdy), iy1 = min(6, 6 + tdy), ix0 = max(0, tdx), ix1 = min(6, 6 + tdx);
-  for (int bw = blockIdx.x / g.heads; bw < B * g.nW; bw += stride) {
-    const int b = bw / g.nW, win = bw % g.nW, wy = win / g.nWw, wx = win % g.nWw;
-    __syncthreads();
-    if (tid < WN) {
-      const TokPos me = win_token(g, wy, wx, tid);
-      sLab[tid] = me.label;
-      sTok[tid] = me.pad ? -1 : (int)me.tok;
-    }
-    __syncthreads();
+  TileRegs pre;
+  float4 o_a, o_b;
+  if (bw < nitem) {
+    stage_load(pre, qkv, qkv_b, dout, g, bw / g.nW, head, sTok[0], w, lane);
+    delta_rows_load(o_a, o_b, outp, g, bw / g.nW, head, sTok[0], tid);
+    wait_loads();
+    stage_store(pre, sQ, sK, sV, sG, scale, w, lane);
+  }
+  int cur = 0;
+  for (; bw < nitem; bw += stride) {
+    const int b = bw / g.nW;
+    const int nxt = cur == 2 ? 0 : cur + 1;
+    const bool more = bw + stride < nitem;  // the ONLY gate of anything indexed by the next item
+    const int* tok_cur = sTok[cur];
+    const unsigned long long pads = sPadm[cur][0] | ((unsigned long long)sPadm[cur][1] << 32);  // (uniform)
+    const int tid = item_tid(), lane = tid & 63, w = tid >> 6, fr = lane & 31;
     // delta_i = sum_j P_ij dP_ij = dO_i . O_i (O = the forward output of this head): with the forward output at hand
     // it is a 32-channel dot product per row (four lanes per row) instead of a cross-lane reduction per dS row
-    float4 o_a = make_float4(0.f, 0.f, 0.f, 0.f), o_b = o_a;
-    if (outp && (tid >> 2) < WN) {
-      const int tok = sTok[tid >> 2];
-      if (tok >= 0) {
-        const float4* o4 = reinterpret_cast<const float4*>(outp + ((long)b * L + tok) * g.C + head * HD + (tid & 3) * 8);
-        o_a = o4[0];
-        o_b = o4[1];
-      }
-    }
-    stage_item_tiles(sQ, sK, sV, sG, qkv + (long)b * L * 3 * g.C + head * HD, qkv_b, dout + (long)b * L * g.C + head * HD, g,
-                     head, sTok, scale, w, lane);
+    const float4 c_a = o_a, c_b = o_b;
+    if (more) token_map(g, bw + stride, sLab[nxt], sTok[nxt], sPadm[nxt], tid);
     __syncthreads();
+    if (more) {
+      stage_load(pre, qkv, qkv_b, dout, g, (bw + stride) / g.nW, head, sTok[nxt], w, lane);
+      delta_rows_load(o_a, o_b, outp, g, (bw + stride) / g.nW, head, sTok[nxt], tid);
+    }
     float* dq_base = dqkv + (long)b * L * 3 * g.C + head * HD;
     if (outp) {
       const float* gq = sG + min(tid >> 2, WN - 1) * LDT + (tid & 3) * 8;
-      float d = ((o_a.x * gq[0] + o_a.y * gq[1]) + (o_a.z * gq[2] + o_a.w * gq[3])) +
-                ((o_b.x * gq[4] + o_b.y * gq[5]) + (o_b.z * gq[6] + o_b.w * gq[7]));
+      float d = ((c_a.x * gq[0] + c_a.y * gq[1]) + (c_a.z * gq[2] + c_a.w * gq[3])) +
+                ((c_b.x * gq[4] + c_b.y * gq[5]) + (c_b.z * gq[6] + c_b.w * gq[7]));
       d += __shfl_xor(d, 1, 64);
       d += __shfl_xor(d, 2, 64);
       if ((tid & 3) == 0) sDelta[tid >> 2] = d;  // (read after the barriers below)
@@ -325,30 +454,20 @@ __device__ __forceinline__ void swin_wattn_bwd_mfma4_body(const float* __restric
       f32x16 a;
       zero16(a);
       mma_rr1(a, sQ, sK, w >> 1, w & 1, lane);
-      store_scores1(a, sP, sT, sLab, g.shift, w >> 1, w & 1, lane);
+      store_scores1(a, sP, sT, sLab[cur], g.shift, w >> 1, w & 1, lane);
     }
     __syncthreads();
     softmax_rows4(sP, tid);
     __syncthreads();
-    // ---- 2. waves 0,1: dP rows of tile w (both column tiles, registers); waves 2,3: dV rows of tile w - 2
+    // ---- 2. waves 0,1: dP rows of tile w (both column tiles, registers); waves 2,3: dV rows of tile w - 2 (registers)
     f32x16 dp[2];
     if (w < 2) {
       zero16(dp[0]); zero16(dp[1]);
       mma_rr1(dp[0], sG, sV, w, 0, lane);
       mma_rr1(dp[1], sG, sV, w, 1, lane);
     } else {
-      f32x16 dv;
-      zero16(dv);
-      mma_ptT1(dv, sP, sG, w - 2, lane);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int j = (w - 2) * 32 + crow(r, lane);
-        if (j < WN) {
-          const int tok = sTok[j];
-          if (tok >= 0) { dq_base[(long)tok * 3 * g.C + 2 * g.C + fr] = dv[r]; amx = fmaxf(amx, fabsf(dv[r])); }
-          else accB[2] += dv[r];
-        }
-      }
+      zero16(dp[0]);
+      mma_ptT1(dp[0], sP, sG, w - 2, lane);
     }
     __syncthreads();  // P has been consumed as an MFMA operand before the rows overwrite it with dS
     if (w < 2) {      // ---- 3. delta_i = sum_j P_ij dP_ij, dS = P (dP - delta) -> sP
@@ -365,37 +484,41 @@ __device__ __forceinline__ void swin_wattn_bwd_mfma4_body(const float* __restric
           if (j1 < WN) sP[i * LDP + j1] = p1 * (dp[1][r] - delta);
         }
       }
+    } else {  // ... meanwhile waves 2,3 send the dV rows out through sV (dead: dP is done).  Each of the two reads back
+      // only the rows it wrote itself (32 (w - 2) .. + 31), so no barrier stands between its LDS writes and reads
+      acc_to_tile(dp[0], sV, 1.f, w - 2, lane, pads, accB[2]);
+      const int p0 = (w - 2) * 32 * (HD / 4) + lane;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (p0 + i * 64 < WN * (HD / 4)) amx = tile_row_piece(sV, dq_base + 2 * g.C, 3 * g.C, tok_cur, p0 + i * 64, amx);
     }
     __syncthreads();
-    if (w < 2) {  // ---- 4. dQ = scale * dS K   (rows = query i)
+    if (w < 2) {  // ---- 4. dQ = scale * dS K   (rows = query i) -> sV (the dV rows left it before the barrier above)
       f32x16 dq;
       zero16(dq);
       mma_pt1(dq, sP, sK, w, lane);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int i = w * 32 + crow(r, lane);
-        if (i < WN) {
-          const int tok = sTok[i];
-          if (tok >= 0) { dq_base[(long)tok * 3 * g.C + fr] = dq[r] * scale; amx = fmaxf(amx, fabsf(dq[r] * scale)); }
-          else accB[0] += dq[r] * scale;
-        }
-      }
-    } else {      // ---- 5. dK = dS^T (q * scale)   (rows = key j; sQ already holds q * scale)
+      acc_to_tile(dq, sV, scale, w, lane, pads, accB[0]);
+    } else {      // ---- 5. dK = dS^T (q * scale)   (rows = key j; sQ already holds q * scale) -> sG (dead since dP / dV)
       f32x16 dk;
       zero16(dk);
       mma_ptT1(dk, sP, sQ, w - 2, lane);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int j = (w - 2) * 32 + crow(r, lane);
-        if (j < WN) {
-          const int tok = sTok[j];
-          if (tok >= 0) { dq_base[(long)tok * 3 * g.C + g.C + fr] = dk[r]; amx = fmaxf(amx, fabsf(dk[r])); }
-          else accB[1] += dk[r];
-        }
-      }
+      acc_to_tile(dk, sG, 1.f, w - 2, lane, pads, accB[1]);
     }
+    __syncthreads();
+    // the wait for the prefetched tiles stands BEFORE the dQ / dK rows are stored: it covers the prefetch (and the dV rows,
+    // two phases old), and these stores stay in flight through the next item
+    wait_loads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i)  // dQ rows, dK rows
+      if (tid + i * 256 < WN * (HD / 4)) {
+        amx = tile_row_piece(sV, dq_base, 3 * g.C, tok_cur, tid + i * 256, amx);
+        amx = tile_row_piece(sG, dq_base + g.C, 3 * g.C, tok_cur, tid + i * 256, amx);
+      }
+    __syncthreads();  // sV / sG have been read: the tiles of the next item may replace them
+    if (more) stage_store(pre, sQ, sK, sV, sG, scale, w, lane);
     if (tid < TBL) {  // bias-table gradient: entry (dy, dx) = sum of dS over the pairs i - j = (dy, dx), fixed order
-      // (constant trip counts + predicates: the 49 LDS reads are issued together instead of one dependent read per add)
+      // (constant trip counts + predicates: the 49 LDS reads are issued together instead of one dependent read per add;
+      // sP keeps dS until the S tiles of the next item, which are behind the next barrier)
       float acc7 = 0.f;
 #pragma unroll 1
       for (int iy = iy0; iy <= iy1; ++iy) {  // (seven reads in flight per row of the window: registers)
@@ -409,25 +532,28 @@ __device__ __forceinline__ void swin_wattn_bwd_mfma4_body(const float* __restric
       }
       dT += acc7;
     }
+    cur = nxt;
   }
   // this workgroup's share of the bias-table / pad-token (qkv-bias) gradients: one partial row, folded over the
   // workgroups of the head in fixed order by wattn_param_fold_kernel
+  __syncthreads();  // (the table gather of the last item has read sP: its memory now carries the fold of the pad-token sums)
+  float(*sBw)[3 * HD] = reinterpret_cast<float(*)[3 * HD]>(sP);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const float other = __shfl_xor(accB[k], 32, 64);
     if (lane < 32) sBw[w][k * HD + fr] = accB[k] + other;
   }
   __syncthreads();
-  float* prow = part + (long)blockIdx.x * WATTN_PROW;
   if (tid < TBL) prow[tid] = dT;
   if (tid < 3 * HD) prow[WATTN_PBIAS + tid] = ((sBw[0][tid] + sBw[1][tid]) + sBw[2][tid]) + sBw[3][tid];
   amax_commit(amax_out, amx);
 }
 
-// Resident workgroups per CU = wavefronts per SIMD: LDS allows four (39 KB each); the registers decide — 2: 202 VGPRs, no
-// scratch; 3: 168 + 92 B of scratch per lane; 4: 128 + 252 B (always loses).  OCC picks the budget (rscotr_swin_wattn_bwd).
-template <int OCC>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void swin_wattn_bwd_mfma4_kernel(
+// Resident workgroups per CU = wavefronts per SIMD: four.  123 VGPRs without scratch and 37.5 KB of LDS allow it; that is
+// why the results leave through the dead operand tiles (sV, sG) and not through tiles of their own (50 KB: three per CU).
+// Measured per stage (profiles/README.md), two -> three -> four per CU: level where every workgroup has one item and fits
+// anyway (stages 3, 4 of Swin-T at 512^2); 80 -> 76 -> 60 us and 52 -> 44 -> 40 us where workgroups loop (stages 1, 2).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void swin_wattn_bwd_mfma4_kernel(
     const float* __restrict__ qkv, const float* __restrict__ qkv_b, const float* __restrict__ table,
     const float* __restrict__ dout, const float* __restrict__ outp, float* __restrict__ dqkv, float* __restrict__ part,
     WinGeom g, int B, unsigned* __restrict__ amax_out) {
@@ -572,11 +698,8 @@ extern "C" int rscotr_swin_wattn_bwd(const float* qkv, const float* qkv_bias, co
   // algorithmic work: S = q k^T (recomputed), dP = dO v^T, dV = P^T dO, dQ = dS k, dK = dS^T q: 10 * 49 * 49 * 32 flop per item
   const double items = (double)B * ((H + ws - 1) / ws) * ((W + ws - 1) / ws) * heads;
   ProfScope prof(PROF_MFMA, items * 10.0 * 49 * 49 * 32, s, "rscotr::swin_wattn_bwd_kernel");
-  // measured (B = 2 at 512^2): 2 resident workgroups per CU win except where the items fit the chip at 3 per CU but not
-  // at 2 (stage 3: 600 items, 35.7 -> 28.9 us); 4 (with scratch) always loses
   const float* o = (out && aligned16(out)) ? out : nullptr;
-  if (nwg > 512 && nwg <= 768) swin_wattn_bwd_mfma4_kernel<3><<<nwg, 256, 0, s>>>(qkv, qkv_bias, bias_table, dout, o, dqkv, workspace, g, B, amax_out);
-  else swin_wattn_bwd_mfma4_kernel<2><<<nwg, 256, 0, s>>>(qkv, qkv_bias, bias_table, dout, o, dqkv, workspace, g, B, amax_out);
+  swin_wattn_bwd_mfma4_kernel<<<nwg, 256, 0, s>>>(qkv, qkv_bias, bias_table, dout, o, dqkv, workspace, g, B, amax_out);
   if (dbias_table || dqkv_bias)
     wattn_param_fold_kernel<<<dim3((WATTN_PROW + 63) / 64, heads), 256, 0, s>>>(workspace, dbias_table, dqkv_bias, heads, C,
                                                                               nwg / heads);
