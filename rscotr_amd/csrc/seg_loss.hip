@@ -7,10 +7,9 @@
 // The reference materialises the upsampled logits — (2,100,512,512) fp32 = 210 MB written, read by
 // log-softmax, NLL, arg-max, and again in backward.  Here a pixel's C interpolated logits only ever
 // exist in registers: forward reads the (B,C,h,w) logits (3.3 MB) and the labels, writes one
-// log-sum-exp per pixel (for backward) and three scalars; backward is a GATHER per low-resolution
-// cell (no atomics): lane = class, loop over the <= (2*sy)x(2*sx) output pixels the cell touches.
-//
-// The resize's source index (src_index) and the gather's block geometry are in seg_upsample.h, shared with csrc/seg_dice.hip.
+// log-sum-exp per pixel (for backward) and three scalars; backward is a GATHER per block of low-resolution cells (no atomics).
+// The resize's source index (src_index), a pixel's 2 x 2 taps and the body of that gather are in seg_upsample.h, shared with
+// csrc/seg_dice.hip; this file supplies the cross-entropy's gradient term (CeTerm).
 #include "seg_upsample.h"
 
 namespace rscotr {
@@ -31,16 +30,13 @@ __global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(const float* __res
   float loss = 0.f, correct = 0.f, valid = 0.f;
   for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
     const int x = (int)(p % W), y = (int)((p / W) % H), b = (int)(p / ((long)W * H));
-    const Interp iy = src_index(y, sy, h), ix = src_index(x, sx, w);
-    const float w00 = iy.l0 * ix.l0, w01 = iy.l0 * ix.l1, w10 = iy.l1 * ix.l0, w11 = iy.l1 * ix.l1;
+    const Taps taps(y, x, sy, sx, h, w);
     const float* base = logit + (long)b * C * h * w;
-    const int o00 = iy.i0 * w + ix.i0, o01 = iy.i0 * w + ix.i1, o10 = iy.i1 * w + ix.i0, o11 = iy.i1 * w + ix.i1;
     const long lab = label[p];
     float m = -3.0e38f, s = 0.f, best = -3.0e38f, at_label = 0.f;
     int arg = 0;
     for (int c = 0; c < C; ++c) {
-      const float* pc = base + (long)c * h * w;
-      const float v = w00 * pc[o00] + w01 * pc[o01] + w10 * pc[o10] + w11 * pc[o11];
+      const float v = taps.at(base + (long)c * h * w);
       if (v > best) { best = v; arg = c; }
       if (c == lab) at_label = v;
       if (v > m) { s = s * __expf(m - v) + 1.f; m = v; }
@@ -92,230 +88,35 @@ __global__ __launch_bounds__(256) void upsample_ce_sums_kernel(const float* __re
   if (threadIdx.x < 3) sums[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// Backward: dlogit[b,c,cy,cx] = scale * sum over output pixels p touching the cell of  wt(p->cell) * (softmax_c(p) - [c == label_p]).
-// Round 5: one workgroup per BLOCK of UCE_TB x UCE_TB low-resolution cells instead of one per cell.  The output pixels whose
-// 2 x 2 tap footprint meets the block — (UCE_TB + 1) * 8 = 40 per axis at the step's x8 resize, 1.56 x the pixels the block
-// owns — are visited ONCE per class (the per-cell kernel visited every pixel from each of the four cells it touches and
-// re-interpolated its logits each time: 245 us at 2 x 100 x 64 x 64 -> 512^2).  512 threads = 4 row groups x 128 class lanes:
-// group g takes the footprint rows y_lo + g, + 4, ...; a lane keeps the four cell sums of the current (row pair, column
-// pair) in registers and folds them into its private LDS column when the column pair changes (every ~8 pixels); the
-// (UCE_TB + 2)^2 cell neighbourhood of all classes, the labels and log-sum-exps of the footprint and the row / column
-// interpolation tables are staged in LDS once.  The four groups meet in fixed order: no atomics, bit-reproducible.
-// (UCE_TB, UCE_NB = UCE_TB + 2 and UCE_FP, the staged footprint edge: seg_upsample.h)
-
-// WT (rscotr_upsample_ce_w_bwd): every pixel's softmax - one-hot is multiplied by pixw[p] (class weight x sampling mask); a
-// pixel of weight 0 is staged as ignored.  The weights of a staged footprint take UCE_FP^2 more floats of LDS (80 KB in all:
-// still two workgroups per CU).
+// Backward: the blocked gather of seg_upsample.h with softmax_c(p) - [c == label_p] as the term; an ignored pixel is skipped.
+// WT (rscotr_upsample_ce_w_bwd): every pixel's softmax - one-hot is multiplied by pixw[p] (class weight x sampling mask), staged
+// as the gather's plane (UCE_FP^2 more floats of LDS, 80 KB in all: still two workgroups per CU); a pixel of weight 0 is staged
+// as ignored.
 template <bool WT>
-__global__ __launch_bounds__(512) void upsample_ce_bwd_kernel(const float* __restrict__ logit,
-                                                              const int64_t* __restrict__ label,
-                                                              const float* __restrict__ lse,
-                                                              const float* __restrict__ gscale, float* __restrict__ dlogit,
-                                                              int B, int C, int h, int w, int H, int W, int ignore,
-                                                              const float* __restrict__ pixw) {
-  extern __shared__ __attribute__((aligned(16))) float uce_smem[];
-  float* sN = uce_smem;                                  // [UCE_NB * UCE_NB][128]   neighbourhood logits of the 128 classes of a pass
-  float* sAcc = sN + UCE_NB * UCE_NB * 128;              // [4 groups][UCE_TB * UCE_TB][128]
-  int2* sLL = reinterpret_cast<int2*>(sAcc + 4 * UCE_TB * UCE_TB * 128);  // [UCE_FP * UCE_FP] {label, bits of lse * log2 e} of a footprint pixel
-  float* sYl = reinterpret_cast<float*>(sLL + UCE_FP * UCE_FP);    // [UCE_FP][2]  l0, l1 of a footprint row
-  int* sYi = reinterpret_cast<int*>(sYl + 2 * UCE_FP);   // [UCE_FP][2]  i0, i1 relative to the block's first cell - 1
-  int4* sXT = reinterpret_cast<int4*>(sYi + 2 * UCE_FP);  // [UCE_FP] {i0, i1 (same origin), bits of l0, l1} of a footprint column
-  float* sPW = reinterpret_cast<float*>(sXT + UCE_FP);   // WT only: [UCE_FP * UCE_FP] weight of a footprint pixel
-  const int bw = (w + UCE_TB - 1) / UCE_TB, bh = (h + UCE_TB - 1) / UCE_TB;
-  const int blk = blockIdx.x;
-  const int cx0 = (blk % bw) * UCE_TB, cy0 = ((blk / bw) % bh) * UCE_TB, b = blk / (bw * bh);
-  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-  // output rows / columns whose taps can include a cell of the block: source coordinate in (c0 - 1, c0 + TB)
-  const int y_lo = max(0, (int)floorf(((float)cy0 - 1.f + 0.5f) / sy - 0.5f));
-  const int y_hi = min(H - 1, (int)ceilf(((float)(cy0 + UCE_TB) + 0.5f) / sy - 0.5f));
-  const int x_lo = max(0, (int)floorf(((float)cx0 - 1.f + 0.5f) / sx - 0.5f));
-  const int x_hi = min(W - 1, (int)ceilf(((float)(cx0 + UCE_TB) + 0.5f) / sx - 0.5f));
-  const int ny = y_hi - y_lo + 1, nx = x_hi - x_lo + 1;
-  const bool staged = ny <= UCE_FP && nx <= UCE_FP;  // uniform
-  const int tid = threadIdx.x, lane = tid & 127, grp = tid >> 7;
-  const float* base = logit + (long)b * C * h * w;
-  const float scale = gscale[0];
-  if (staged) {
-    for (int i = tid; i < ny * nx; i += 512) {
-      const long p = ((long)b * H + y_lo + i / nx) * W + x_lo + i % nx;
-      if constexpr (WT) {
-        const float pw = pixw[p];
-        sPW[i] = pw;
-        sLL[i] = make_int2(pw == 0.f ? ignore : (int)label[p], __float_as_int(lse[p] * 1.4426950408889634f));
-      } else {
-        sLL[i] = make_int2((int)label[p], __float_as_int(lse[p] * 1.4426950408889634f));  // (the staged path works in the log2 domain: one v_exp_f32 per pixel and class)
-      }
-    }
+struct CeTerm {
+  static constexpr bool PLANE = WT;
+  const int64_t* __restrict__ label;
+  const float* __restrict__ pixw;  // WT only
+  int ignore;
+  __device__ __forceinline__ void load_class(int, int) {}
+  __device__ __forceinline__ int stage(long p, float& plane) const {
+    if constexpr (WT) plane = pixw[p];
+    return WT && plane == 0.f ? ignore : (int)label[p];
   }
-  for (int i = tid; i < min(ny, UCE_FP); i += 512) {
-    const Interp iy = src_index(y_lo + i, sy, h);
-    sYl[2 * i] = iy.l0; sYl[2 * i + 1] = iy.l1;
-    sYi[2 * i] = iy.i0 - cy0 + 1; sYi[2 * i + 1] = iy.i1 - cy0 + 1;
+  __device__ __forceinline__ bool skip(int lab) const { return lab == ignore; }
+  __device__ __forceinline__ float term(float prob, int c, int lab, float plane) const {
+    const float gq = prob - (c == lab ? 1.f : 0.f);
+    return WT ? gq * plane : gq;
   }
-  for (int i = tid; i < min(nx, UCE_FP); i += 512) {
-    const Interp ix = src_index(x_lo + i, sx, w);
-    sXT[i] = make_int4(ix.i0 - cx0 + 1, ix.i1 - cx0 + 1, __float_as_int(ix.l0), __float_as_int(ix.l1));
-  }
-  for (int c0 = 0; c0 < C; c0 += 128) {
-    const int c = c0 + lane;
-    __syncthreads();
-    // neighbourhood (cells cy0 - 1 .. cy0 + TB, cx0 - 1 .. cx0 + TB; zeros outside the map: never weighted) of this pass's classes
-    for (int k = grp; k < UCE_NB * UCE_NB; k += 4) {
-      const int ny_ = cy0 + k / UCE_NB - 1, nx_ = cx0 + k % UCE_NB - 1;
-      sN[k * 128 + lane] = (c < C && ny_ >= 0 && ny_ < h && nx_ >= 0 && nx_ < w) ? base[(long)c * h * w + ny_ * w + nx_] : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < UCE_TB * UCE_TB; ++k) sAcc[(grp * UCE_TB * UCE_TB + k) * 128 + lane] = 0.f;
-    __syncthreads();
-    if (c < C && staged) {
-      // Staged footprints (the step's shapes).  Everything that depends on the pixel alone — tap indices and weights, label,
-      // log-sum-exp — is the same for the 64 lanes of a wavefront (a row group is two whole wavefronts): read to scalar
-      // registers.  The footprint columns are walked one COLUMN PAIR (first tap on block column k - 1, k = 0 .. TB) at a time,
-      // the pair loop unrolled: the vector work per pixel and class is the interpolation (2 FMAs on the row-combined cell
-      // logits A0 / A1 of the pair), one exp2, the one-hot and two FMAs into the pair's sums s0 / s1, which land in the row's
-      // column sums cs[] by static register index; the row weights multiply cs once per row and only then touch the thread's
-      // LDS cells (8 read-add-writes per footprint row; the first cut folded 4 per column pair: 151 -> 118 us at
-      // 2 x 100 x 64 x 64 -> 512^2, this form: see profiles/README.md)
-      float* acc = sAcc + grp * UCE_TB * UCE_TB * 128 + lane;
-      auto sc = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
-      auto scf = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
-      int xs[UCE_TB + 2];  // xs[k] = first footprint column whose first tap is block column >= k - 1 (columns ascend with xx)
-#pragma unroll
-      for (int k = 0; k < UCE_TB + 2; ++k) xs[k] = 0;
-      for (int xx = 0; xx < nx; ++xx) {
-        const int kx0 = sc(sXT[xx].x);
-#pragma unroll
-        for (int k = 0; k < UCE_TB + 2; ++k) xs[k] += kx0 < k ? 1 : 0;
-      }
-      for (int r = grp; r < ny; r += 4) {
-        const int ky0 = sc(sYi[2 * r]), ky1 = sc(sYi[2 * r + 1]);
-        const float yl0 = scf(sYl[2 * r]), yl1 = scf(sYl[2 * r + 1]);
-        const bool in0 = ky0 >= 1 && ky0 <= UCE_TB && cy0 + ky0 - 1 < h, in1 = ky1 >= 1 && ky1 <= UCE_TB && cy0 + ky1 - 1 < h;
-        if (!in0 && !in1) continue;
-        const int b0 = min(max(ky0, 0), UCE_NB - 1), b1 = min(max(ky1, 0), UCE_NB - 1);
-        const int2* llr = sLL + r * nx;
-        const float* pwr = sPW + r * nx;  // (WT only)
-        float cs[UCE_TB + 2];  // column sums of this row by block column + 1 (0 and TB + 1: the halo, dropped)
-#pragma unroll
-        for (int k = 0; k < UCE_TB + 2; ++k) cs[k] = 0.f;
-#pragma unroll
-        for (int k = 0; k <= UCE_TB; ++k) {  // pairs (k, k + 1); at the far edge of the map (k, k)
-          const int x0 = xs[k], x1 = xs[k + 1];
-          if (x0 == x1) continue;  // (uniform)
-          const int kx1 = sc(sXT[x0].y);
-          const int a1 = min(max(kx1, 0), UCE_NB - 1);
-          const float n00 = sN[(b0 * UCE_NB + k) * 128 + lane], n01 = sN[(b0 * UCE_NB + a1) * 128 + lane];
-          const float n10 = sN[(b1 * UCE_NB + k) * 128 + lane], n11 = sN[(b1 * UCE_NB + a1) * 128 + lane];
-          const float A0 = (yl0 * n00 + yl1 * n10) * 1.4426950408889634f;
-          const float A1 = (yl0 * n01 + yl1 * n11) * 1.4426950408889634f;
-          float s0 = 0.f, s1 = 0.f;
-          // one 16-byte column record + one 8-byte pixel record per step, the next step's pair requested before this one is used
-          int4 xt_n = sXT[x0];
-          int2 ll_n = llr[x0];
-          float pw_n = 0.f;
-          if constexpr (WT) pw_n = pwr[x0];
-          for (int xx = x0; xx < x1; ++xx) {
-            const int4 xt = xt_n;
-            const int2 ll = ll_n;
-            const float pw = pw_n;
-            const int xn = min(xx + 1, nx - 1);
-            xt_n = sXT[xn];
-            ll_n = llr[xn];
-            if constexpr (WT) pw_n = pwr[xn];
-            const int lab = sc(ll.x);
-            if (lab == ignore) continue;
-            const float xl0 = __int_as_float(sc(xt.z)), xl1 = __int_as_float(sc(xt.w));
-            const float ls = __int_as_float(sc(ll.y));
-            float gq = __builtin_amdgcn_exp2f(fmaf(xl1, A1, fmaf(xl0, A0, -ls))) - (c == lab ? 1.f : 0.f);
-            if constexpr (WT) gq *= scf(pw);
-            s0 = fmaf(xl0, gq, s0);
-            s1 = fmaf(xl1, gq, s1);
-          }
-          cs[k] += s0;
-          if (kx1 == k) cs[k] += s1; else cs[k + 1] += s1;  // (uniform)
-        }
-#pragma unroll
-        for (int k = 1; k <= UCE_TB; ++k) {
-          if (cx0 + k - 1 < w) {
-            if (in0) acc[((ky0 - 1) * UCE_TB + k - 1) * 128] += yl0 * cs[k];
-            if (in1) acc[((ky1 - 1) * UCE_TB + k - 1) * 128] += yl1 * cs[k];
-          }
-        }
-      }
-    } else if (c < C) {
-      float* acc = sAcc + grp * UCE_TB * UCE_TB * 128 + lane;
-      for (int r = grp; r < ny; r += 4) {
-        int ky0, ky1;
-        float yl0, yl1;
-        if (r < UCE_FP) { ky0 = sYi[2 * r]; ky1 = sYi[2 * r + 1]; yl0 = sYl[2 * r]; yl1 = sYl[2 * r + 1]; }
-        else { const Interp iy = src_index(y_lo + r, sy, h); ky0 = iy.i0 - cy0 + 1; ky1 = iy.i1 - cy0 + 1; yl0 = iy.l0; yl1 = iy.l1; }
-        // (a row whose both taps lie outside the block contributes nothing; the footprint bounds are conservative)
-        const bool in0 = ky0 >= 1 && ky0 <= UCE_TB && cy0 + ky0 - 1 < h, in1 = ky1 >= 1 && ky1 <= UCE_TB && cy0 + ky1 - 1 < h;
-        if (!in0 && !in1) continue;
-        float t00 = 0.f, t01 = 0.f, t10 = 0.f, t11 = 0.f;
-        int cur0 = -100, cur1 = -100;
-        auto flush = [&]() {
-          if (cur0 == -100) return;
-          const bool jx0 = cur0 >= 1 && cur0 <= UCE_TB && cx0 + cur0 - 1 < w, jx1 = cur1 >= 1 && cur1 <= UCE_TB && cx0 + cur1 - 1 < w;
-          if (in0 && jx0) acc[((ky0 - 1) * UCE_TB + cur0 - 1) * 128] += t00;
-          if (in0 && jx1) acc[((ky0 - 1) * UCE_TB + cur1 - 1) * 128] += t01;
-          if (in1 && jx0) acc[((ky1 - 1) * UCE_TB + cur0 - 1) * 128] += t10;
-          if (in1 && jx1) acc[((ky1 - 1) * UCE_TB + cur1 - 1) * 128] += t11;
-          t00 = t01 = t10 = t11 = 0.f;
-        };
-        float n00 = 0.f, n01 = 0.f, n10 = 0.f, n11 = 0.f;
-        for (int xx = 0; xx < nx; ++xx) {
-          int kx0, kx1;
-          float xl0, xl1;
-          if (xx < UCE_FP) { const int4 xt = sXT[xx]; kx0 = xt.x; kx1 = xt.y; xl0 = __int_as_float(xt.z); xl1 = __int_as_float(xt.w); }
-          else { const Interp ix = src_index(x_lo + xx, sx, w); kx0 = ix.i0 - cx0 + 1; kx1 = ix.i1 - cx0 + 1; xl0 = ix.l0; xl1 = ix.l1; }
-          if (kx0 != cur0 || kx1 != cur1) {  // a new column pair: fold the finished one, fetch this one's four cell logits
-            flush();
-            cur0 = kx0; cur1 = kx1;
-            const int a0 = min(max(kx0, 0), UCE_NB - 1), a1 = min(max(kx1, 0), UCE_NB - 1);
-            const int b0 = min(max(ky0, 0), UCE_NB - 1), b1 = min(max(ky1, 0), UCE_NB - 1);
-            n00 = sN[(b0 * UCE_NB + a0) * 128 + lane]; n01 = sN[(b0 * UCE_NB + a1) * 128 + lane];
-            n10 = sN[(b1 * UCE_NB + a0) * 128 + lane]; n11 = sN[(b1 * UCE_NB + a1) * 128 + lane];
-          }
-          int lab;
-          float ls;
-          { const long p = ((long)b * H + y_lo + r) * W + x_lo + xx; lab = (int)label[p]; ls = lse[p]; }  // (footprints past the staged size)
-          if (lab == ignore) continue;
-          float pw = 1.f;
-          if constexpr (WT) {
-            pw = pixw[((long)b * H + y_lo + r) * W + x_lo + xx];
-            if (pw == 0.f) continue;
-          }
-          const float v = yl0 * (xl0 * n00 + xl1 * n01) + yl1 * (xl0 * n10 + xl1 * n11);
-          float gq = __expf(v - ls) - (c == lab ? 1.f : 0.f);
-          if constexpr (WT) gq *= pw;
-          t00 += yl0 * xl0 * gq; t01 += yl0 * xl1 * gq; t10 += yl1 * xl0 * gq; t11 += yl1 * xl1 * gq;
-        }
-        flush();
-      }
-    }
-    __syncthreads();
-    // the four row groups meet in fixed order; thread (grp, lane) writes block rows grp of class lane
-    if (c < C && cy0 + grp < h) {
-      float* drow = dlogit + ((long)b * C + c) * h * w + (long)(cy0 + grp) * w + cx0;
-#pragma unroll
-      for (int k = 0; k < UCE_TB; ++k) {
-        if (cx0 + k < w) {
-          float v = 0.f;
-#pragma unroll
-          for (int g2 = 0; g2 < 4; ++g2) v += sAcc[((g2 * UCE_TB + grp) * UCE_TB + k) * 128 + lane];
-          drow[k] = v * scale;
-        }
-      }
-    }
-  }
-}
+};
 
-constexpr size_t uce_bwd_lds_bytes(bool weighted = false) {
-  return (size_t)(UCE_NB * UCE_NB * 128 + 4 * UCE_TB * UCE_TB * 128 + 2 * UCE_FP * UCE_FP + 8 * UCE_FP +
-                  (weighted ? UCE_FP * UCE_FP : 0)) * 4;
+template <bool WT>
+__global__ __launch_bounds__(512) void upsample_ce_bwd_kernel(const float* __restrict__ logit, const int64_t* __restrict__ label,
+                                                              const float* __restrict__ lse, const float* __restrict__ gscale,
+                                                              float* __restrict__ dlogit, int B, int C, int h, int w, int H, int W,
+                                                              int ignore, const float* __restrict__ pixw) {
+  upsample_gather(CeTerm<WT>{label, pixw, ignore}, logit, lse, gscale, dlogit, C, h, w, H, W);
 }
-static_assert(2 * uce_bwd_lds_bytes(true) <= 160 * 1024, "two weighted backward workgroups per CU");
 
 // ---- online hard example mining (mmseg OHEMPixelSampler with a probability threshold) ---------------------------------------
 // A valid pixel is kept when prob_p < max(kth, thresh), kth = the min(kept, N_valid - 1)-th smallest prob_p = exp(-nll_p) over
@@ -470,8 +271,7 @@ extern "C" int64_t rscotr_upsample_ce_workspace(void) { return (int64_t)UCE_MAX_
 extern "C" int rscotr_upsample_ce_fwd(const float* logit, const int64_t* label, float* lse, float* sums, int B,
                                       int C, int h, int w, int H, int W, int ignore_index, float* workspace,
                                       int64_t workspace_bytes, void* stream) {
-  if (B < 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0)
-    return fail(RSCOTR_E_SHAPE, "rscotr_upsample_ce_fwd: bad shape");
+  if (int e = upsample_check_shape("rscotr_upsample_ce_fwd", B, C, h, w, H, W)) return e;
   if (!sums) return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_fwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
   if (B == 0) {
@@ -494,20 +294,11 @@ extern "C" int rscotr_upsample_ce_fwd(const float* logit, const int64_t* label, 
 extern "C" int rscotr_upsample_ce_bwd(const float* logit, const int64_t* label, const float* lse,
                                       const float* grad_scale, float* dlogit, int B, int C, int h, int w, int H,
                                       int W, int ignore_index, void* stream) {
-  if (B < 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0)
-    return fail(RSCOTR_E_SHAPE, "rscotr_upsample_ce_bwd: bad shape");
+  if (int e = upsample_check_shape("rscotr_upsample_ce_bwd", B, C, h, w, H, W)) return e;
   if (B == 0) return RSCOTR_OK;
   if (!logit || !label || !lse || !grad_scale || !dlogit) return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_bwd: null pointer");
-  static_assert(UCE_TB == 4, "four row groups write the four cell rows of a block");
-  static const bool attr_set = [] {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(upsample_ce_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)uce_bwd_lds_bytes());
-    return true;
-  }();
-  (void)attr_set;
-  const int nblk = B * ((h + UCE_TB - 1) / UCE_TB) * ((w + UCE_TB - 1) / UCE_TB);
-  upsample_ce_bwd_kernel<false><<<nblk, 512, uce_bwd_lds_bytes(), (hipStream_t)stream>>>(logit, label, lse, grad_scale, dlogit, B,
-                                                                                        C, h, w, H, W, ignore_index, nullptr);
+  launch_upsample_gather<upsample_ce_bwd_kernel<false>, false>((hipStream_t)stream, B, h, w, logit, label, lse, grad_scale, dlogit, B,
+                                                               C, h, w, H, W, ignore_index, nullptr);
   return check_launch("rscotr_upsample_ce_bwd");
 }
 
@@ -518,8 +309,7 @@ extern "C" int64_t rscotr_upsample_ce_w_workspace(void) { return (int64_t)(UCE_M
 extern "C" int rscotr_upsample_ce_w_fwd(const float* logit, const int64_t* label, const float* class_weight, float* lse,
                                         float* nll, float* pix_weight, float* sums, int B, int C, int h, int w, int H, int W,
                                         int ignore_index, float* workspace, int64_t workspace_bytes, void* stream) {
-  if (B < 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0)
-    return fail(RSCOTR_E_SHAPE, "rscotr_upsample_ce_w_fwd: bad shape");
+  if (int e = upsample_check_shape("rscotr_upsample_ce_w_fwd", B, C, h, w, H, W)) return e;
   if (!sums) return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_w_fwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
   if (B == 0) {
@@ -568,20 +358,11 @@ extern "C" int rscotr_upsample_ce_ohem(const int64_t* label, const float* class_
 extern "C" int rscotr_upsample_ce_w_bwd(const float* logit, const int64_t* label, const float* lse, const float* pix_weight,
                                         const float* grad_scale, float* dlogit, int B, int C, int h, int w, int H, int W,
                                         int ignore_index, void* stream) {
-  if (B < 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0)
-    return fail(RSCOTR_E_SHAPE, "rscotr_upsample_ce_w_bwd: bad shape");
+  if (int e = upsample_check_shape("rscotr_upsample_ce_w_bwd", B, C, h, w, H, W)) return e;
   if (B == 0) return RSCOTR_OK;
   if (!logit || !label || !lse || !pix_weight || !grad_scale || !dlogit)
     return fail(RSCOTR_E_ARG, "rscotr_upsample_ce_w_bwd: null pointer");
-  static const bool attr_set = [] {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(upsample_ce_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)uce_bwd_lds_bytes(true));
-    return true;
-  }();
-  (void)attr_set;
-  const int nblk = B * ((h + UCE_TB - 1) / UCE_TB) * ((w + UCE_TB - 1) / UCE_TB);
-  upsample_ce_bwd_kernel<true><<<nblk, 512, uce_bwd_lds_bytes(true), (hipStream_t)stream>>>(logit, label, lse, grad_scale, dlogit,
-                                                                                           B, C, h, w, H, W, ignore_index,
-                                                                                           pix_weight);
+  launch_upsample_gather<upsample_ce_bwd_kernel<true>, true>((hipStream_t)stream, B, h, w, logit, label, lse, grad_scale, dlogit, B, C,
+                                                             h, w, H, W, ignore_index, pix_weight);
   return check_launch("rscotr_upsample_ce_w_bwd");
 }

@@ -189,15 +189,25 @@ def box_loss_sums(pred, target, weight, factors, eps=1e-6):
     return _BoxLoss.apply(pred, target, weight, factors, eps)
 
 
+def _upsample_args(logit, label, class_weight=None):
+    """The opening of the three fused upsample losses: fp32-contiguous logits and class weights, contiguous labels, all on
+    one device, as many class weights as channels -> (logit, label, cw | None, B, C, h, w, H, W, lse (B,H,W) to be written)."""
+    logit = _f32c(logit)
+    label = label.contiguous()
+    cw = None if class_weight is None else _f32c(class_weight)
+    _chk(logit, label, cw)
+    B, C, h, w = logit.shape
+    H, W = label.shape[-2:]
+    if cw is not None and cw.numel() != C:
+        raise ValueError(f'class_weight has {cw.numel()} entries, the logits have {C} channels')
+    lse = torch.empty((B, H, W), dtype=torch.float32, device=logit.device)
+    return logit, label, cw, B, C, h, w, H, W, lse
+
+
 class _UpsampleCE(Function):
     @staticmethod
     def forward(ctx, logit, label, ignore_index):
-        logit = _f32c(logit)
-        label = label.contiguous()
-        _chk(logit, label)
-        B, C, h, w = logit.shape
-        H, W = label.shape[-2:]
-        lse = torch.empty((B, H, W), dtype=torch.float32, device=logit.device)
+        logit, label, _, B, C, h, w, H, W, lse = _upsample_args(logit, label)
         sums = torch.empty(3, dtype=torch.float32, device=logit.device)
         with _Prof('upsample_ce_fwd', 4 * B * C * h * w + 12 * B * H * W):
             nws = lib.rscotr_upsample_ce_workspace()
@@ -240,16 +250,8 @@ class _UpsampleCEWeighted(Function):
 
     @staticmethod
     def forward(ctx, logit, label, ignore_index, class_weight, norm, ohem):
-        logit = _f32c(logit)
-        label = label.contiguous()
-        cw = None if class_weight is None else _f32c(class_weight)
-        _chk(logit, label, cw)
-        B, C, h, w = logit.shape
-        H, W = label.shape[-2:]
-        if cw is not None and cw.numel() != C:
-            raise ValueError(f'class_weight has {cw.numel()} entries, the logits have {C} channels')
+        logit, label, cw, B, C, h, w, H, W, lse = _upsample_args(logit, label, class_weight)
         dev = logit.device
-        lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
         nll, pixw = torch.empty_like(lse), torch.empty_like(lse)
         sums = torch.empty(4, dtype=torch.float32, device=dev)
         nws = lib.rscotr_upsample_ce_w_workspace()
@@ -328,16 +330,8 @@ class _UpsampleDice(Function):
 
     @staticmethod
     def forward(ctx, logit, label, ignore_index, smooth, class_weight, loss_weight):
-        logit = _f32c(logit)
-        label = label.contiguous()
-        cw = None if class_weight is None else _f32c(class_weight)
-        _chk(logit, label, cw)
-        B, C, h, w = logit.shape
-        H, W = label.shape[-2:]
-        if cw is not None and cw.numel() != C:
-            raise ValueError(f'class_weight has {cw.numel()} entries, the logits have {C} channels')
+        logit, label, cw, B, C, h, w, H, W, lse = _upsample_args(logit, label, class_weight)
         dev = logit.device
-        lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
         coef = torch.empty((B, C, 2), dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         nws = lib.rscotr_upsample_dice_workspace(B, C)

@@ -32,6 +32,9 @@ _SHAPES = [
     ('staged_interior_blocks', 1, 2, 13, 11, 50, 37),                 # non-integer ratios
     ('staged', 2, 7, 8, 8, 8, 8),                                     # identity
     ('staged_downsample', 1, 2, 13, 9, 5, 4),                         # untouched cells
+    ('fallback_rows_only_mixed_launch', 1, 2, 5, 6, 70, 30),
+    ('fallback_cols_only', 1, 2, 6, 5, 30, 70),
+    ('fallback_records_recomputed', 1, 2, 3, 3, 150, 150),
 ]
 _BASE = _SHAPES[0][1:]
 

@@ -7,8 +7,9 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-# csrc/seg_loss.hip: cells per block edge of upsample_ce_bwd_kernel, the footprint rows / columns it stages in LDS (a block
-# whose footprint is larger on either axis takes the kernel's second implementation) and the forward grid cap
+# csrc/seg_upsample.h: cells per block edge of the backward gather (upsample_ce_bwd_kernel), the footprint rows / columns it stages
+# in LDS (a block whose footprint is larger on either axis takes the gather's second implementation); csrc/seg_loss.hip: the
+# forward grid cap
 UCE_TB = 4
 UCE_FP = 48
 UCE_MAX_WG = 4096

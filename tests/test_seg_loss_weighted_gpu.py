@@ -25,6 +25,9 @@ _SHAPES = [
     ('staged_interior_blocks', 1, 2, 13, 11, 50, 37),                 # non-integer ratios
     ('staged', 2, 7, 8, 8, 8, 8),                                     # identity
     ('staged_downsample', 1, 2, 13, 9, 5, 4),                         # untouched cells
+    ('fallback_rows_only_mixed_launch', 1, 2, 5, 6, 70, 30),
+    ('fallback_cols_only', 1, 2, 6, 5, 30, 70),
+    ('fallback_records_recomputed', 1, 2, 3, 3, 150, 150),
 ]
 _MODES = [('cw', False, 'mean'), ('cw', True, 'mean'), ('cw', False, 'sum')]
 _NO_SAMPLER = [s + m for s in _SHAPES for m in _MODES[:2]] + [_SHAPES[0] + _MODES[2]]
