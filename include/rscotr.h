@@ -32,7 +32,8 @@ extern "C" {
  * round 6 = 7; 11 added the resampling input entries rscotr_img_aug_u8 / rscotr_seg_label_aug_u8; the
  * evaluation entries since — seg_predict / seg_areas, det_decode / det_match, seg_predict_tta, seg_predict_slide — are additive and change no
  * argument list, so they keep 11: a library without them fails to bind by name; the seg head's scheme-1 entries rscotr_seg_mix_* and
- * the det input chain rscotr_img_aug_chain_u8 likewise, and the Dice seg loss rscotr_upsample_dice_*).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
+ * the det input chain rscotr_img_aug_chain_u8 likewise, and the Dice, Tversky and focal seg losses
+ * rscotr_upsample_dice_* / rscotr_upsample_tversky_* / rscotr_upsample_focal_*).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
  * its first call (rscotr_amd/_lib.py does) — a stale .so would take a stream handle for a pointer. */
 #define RSCOTR_ABI_VERSION 11
 int rscotr_version(void);
@@ -564,6 +565,47 @@ int rscotr_upsample_dice_fwd(const float* logit, const int64_t* label, const flo
 int rscotr_upsample_dice_bwd(const float* logit, const int64_t* label, const float* lse, const float* coef,
                              const float* grad_scale, float* pix_s, float* dlogit, int B, int C, int h, int w, int H, int W,
                              int ignore_index, void* stream);
+
+/* ---- fused bilinear upsample + softmax + Tversky (seg loss; additive entries: the ABI revision is unchanged) ---------------
+ * mmseg 0.28 TverskyLoss as BaseDecodeHead.losses reaches it: the Dice entries' kernels instantiated a second time, with the
+ * Dice entries' buffers, limits and launch counts.  p, t, v as above;
+ *   TP = sum_pix p t v;  FP = sum_pix p (1 - t) v;  FN = sum_pix (1 - p) t v  (all three masked);
+ *   num[b,c] = TP + smooth;  den[b,c] = TP + alpha FP + beta FN + smooth;  smooth > 0, else RSCOTR_E_ARG;
+ *   loss[0] = loss_weight / C * sum_{c != ignore_index} class_weight[c] * mean_b (1 - num / den).
+ *   _fwd writes lse (B,H,W), coef (B,C,2) = {a, bcoef} = {k (num (1 - alpha - beta) / den^2 - 1 / den), k alpha num / den^2}, k as
+ *     above, and loss[0]; workspace: rscotr_upsample_tversky_workspace(B, C) bytes.
+ *   _bwd: dlogit (B,C,h,w) = grad_scale[0] * d(loss)/d(logit), grad_scale a DEVICE scalar: pix_s (B,H,W) = v sum_c (a t + bcoef) p_c
+ *     (the caller's scratch), then the gather with p_c (a t + bcoef - pix_s) over the non-ignored pixels; cells no such pixel
+ *     touches are written as exact zeros. */
+int64_t rscotr_upsample_tversky_workspace(int B, int C);
+int rscotr_upsample_tversky_fwd(const float* logit, const int64_t* label, const float* class_weight, float* lse, float* coef,
+                                float* loss, int B, int C, int h, int w, int H, int W, int ignore_index, float alpha, float beta,
+                                float smooth, float loss_weight, float* workspace, int64_t workspace_bytes, void* stream);
+int rscotr_upsample_tversky_bwd(const float* logit, const int64_t* label, const float* lse, const float* coef,
+                                const float* grad_scale, float* pix_s, float* dlogit, int B, int C, int h, int w, int H, int W,
+                                int ignore_index, void* stream);
+
+/* ---- fused bilinear upsample + sigmoid focal (seg loss; additive entries: the ABI revision is unchanged) -------------------
+ * mmseg 0.28 FocalLoss (py_sigmoid_focal_loss) as BaseDecodeHead.losses reaches it, without the up-sampled logits in memory:
+ *   u = resize(logit, (H,W), bilinear, align_corners=False);  t[b,c,.] = [label == c] (a label outside [0, C) has no positive
+ *   class: mmseg's one_hot would raise on a non-ignored one);  v = [label != ignore_index];  s = sigmoid(u);
+ *   q = (1 - s) t + s (1 - t);  e = BCE_with_logits(u, t) * (alpha_c t + (1 - alpha_c) (1 - t)) * q^gamma * class_weight[c] * v;
+ *   loss[0] = loss_scale * sum e   (the caller's reduction: loss_weight / (B*H*W*C) for 'mean', loss_weight for 'sum').
+ *   logit (B,C,h,w); label (B,H,W) int64; alpha_per_class C floats, or NULL: the scalar `alpha` for every class; class_weight
+ *   C floats or NULL; gamma >= 0 (0: q^0 = 1 everywhere), else RSCOTR_E_ARG.  Stable at any logit: no exp(u), no inf / inf.
+ *   _fwd: one launch over the pixels leaves a partial sum per workgroup in `workspace` (rscotr_upsample_focal_workspace()
+ *     bytes), a second folds them in fixed order (fp64), no atomics: bit-reproducible.  Nothing is saved for backward.
+ *   _bwd: dlogit (B,C,h,w) = grad_scale[0] * d(sum e)/d(logit), grad_scale a DEVICE scalar (upstream gradient * loss_scale): the
+ *     gather of rscotr_upsample_ce_bwd on the interpolated logit itself (no log-sum-exp array); cells no non-ignored pixel
+ *     touches are written as exact zeros.
+ * No entry synchronises with the host or allocates: all of them can be captured in a hipGraph. */
+int64_t rscotr_upsample_focal_workspace(void);
+int rscotr_upsample_focal_fwd(const float* logit, const int64_t* label, const float* alpha_per_class, const float* class_weight,
+                              float* loss, int B, int C, int h, int w, int H, int W, int ignore_index, float gamma, float alpha,
+                              float loss_scale, float* workspace, int64_t workspace_bytes, void* stream);
+int rscotr_upsample_focal_bwd(const float* logit, const int64_t* label, const float* alpha_per_class, const float* class_weight,
+                              const float* grad_scale, float* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index,
+                              float gamma, float alpha, void* stream);
 
 /* Query position embedding of the DINO decoder (models/multi/bbox_head/transformer.py:43-76): pos (rows,4) = (x,y,w,h)
  * -> out (rows,512) = [emb(y)|emb(x)|emb(w)|emb(h)], emb(v)[2i] = sin(2 pi v / 10000^(2i/128)), [2i+1] = cos.  No

@@ -9,7 +9,7 @@
 // exist in registers: forward reads the (B,C,h,w) logits (3.3 MB) and the labels, writes one
 // log-sum-exp per pixel (for backward) and three scalars; backward is a GATHER per block of low-resolution cells (no atomics).
 // The resize's source index (src_index), a pixel's 2 x 2 taps and the body of that gather are in seg_upsample.h, shared with
-// csrc/seg_dice.hip; this file supplies the cross-entropy's gradient term (CeTerm).
+// csrc/seg_dice.hip and csrc/seg_focal.hip; this file supplies the cross-entropy's gradient term (CeTerm).
 #include "seg_upsample.h"
 
 namespace rscotr {
@@ -95,6 +95,7 @@ __global__ __launch_bounds__(256) void upsample_ce_sums_kernel(const float* __re
 template <bool WT>
 struct CeTerm {
   static constexpr bool PLANE = WT;
+  static constexpr bool RAW = false;
   const int64_t* __restrict__ label;
   const float* __restrict__ pixw;  // WT only
   int ignore;

@@ -1,6 +1,7 @@
-// Bilinear resize (align_corners=False) for the fused seg losses (csrc/seg_loss.hip: cross-entropy, csrc/seg_dice.hip: Dice)
-// and the masked-attention mask: the source index, the 2 x 2 taps of an output pixel, the blocked backward gather that both
-// losses instantiate with their own gradient term, and the host helpers of their entries.
+// Bilinear resize (align_corners=False) for the fused seg losses (csrc/seg_loss.hip: cross-entropy, csrc/seg_dice.hip: Dice
+// and Tversky, csrc/seg_focal.hip: sigmoid focal) and the masked-attention mask: the source index, the 2 x 2 taps of an output
+// pixel, the blocked backward gather that every loss instantiates with its own gradient term, and the host helpers of their
+// entries.
 //
 // PyTorch's upsample_bilinear2d (align_corners=False) source index: s = max((d + 0.5) * in/out - 0.5, 0),
 // i0 = floor(s), i1 = min(i0 + 1, in - 1), lambda1 = s - i0.
@@ -63,10 +64,13 @@ static_assert(2 * upsample_gather_lds_bytes(true) <= 160 * 1024, "two backward w
 // The body of a __launch_bounds__(512) kernel with upsample_gather_lds_bytes(Term::PLANE) bytes of dynamic LDS, one workgroup
 // per block of cells.  Term is what a loss supplies:
 //   static constexpr bool PLANE           a per-pixel float is staged with the label (a weight, a per-pixel sum)
+//   static constexpr bool RAW             term() takes the interpolated logit u_c(p) itself instead of softmax_c(p) (a per-element
+//                                         loss: the sigmoid focal, where exp(u) overflows and a sigmoid does not); `lse` is then
+//                                         never read and may be null
 //   void  load_class(b, c)                this lane's class constants of image b (c may be >= C)
 //   int   stage(p, float& plane)          the label output pixel p is staged with, and its plane value (PLANE only)
 //   bool  skip(lab)                       a pixel staged with this label contributes nothing
-//   float term(prob, c, lab, plane)       the gradient term of class c from prob = softmax_c(p)
+//   float term(prob, c, lab, plane)       the gradient term of class c from prob = softmax_c(p) (RAW: from u_c(p))
 // Both implementations below — the staged walk and the one for footprints past UCE_FP — call the same stage / skip / term.
 template <class Term>
 __device__ __forceinline__ void upsample_gather(Term term, const float* __restrict__ logit, const float* __restrict__ lse,
@@ -100,7 +104,8 @@ __device__ __forceinline__ void upsample_gather(Term term, const float* __restri
       float plane = 0.f;
       const int lab = term.stage(p, plane);
       if constexpr (Term::PLANE) sPl[i] = plane;
-      sLL[i] = make_int2(lab, __float_as_int(lse[p] * 1.4426950408889634f));  // (the staged path works in the log2 domain: one v_exp_f32 per pixel and class)
+      if constexpr (Term::RAW) sLL[i] = make_int2(lab, 0);
+      else sLL[i] = make_int2(lab, __float_as_int(lse[p] * 1.4426950408889634f));  // (the staged path works in the log2 domain: one v_exp_f32 per pixel and class)
     }
   }
   for (int i = tid; i < min(ny, UCE_FP); i += 512) {
@@ -163,8 +168,9 @@ __device__ __forceinline__ void upsample_gather(Term term, const float* __restri
           const int a1 = min(max(kx1, 0), UCE_NB - 1);
           const float n00 = sN[(b0 * UCE_NB + k) * 128 + lane], n01 = sN[(b0 * UCE_NB + a1) * 128 + lane];
           const float n10 = sN[(b1 * UCE_NB + k) * 128 + lane], n11 = sN[(b1 * UCE_NB + a1) * 128 + lane];
-          const float A0 = (yl0 * n00 + yl1 * n10) * 1.4426950408889634f;
-          const float A1 = (yl0 * n01 + yl1 * n11) * 1.4426950408889634f;
+          constexpr float dom = Term::RAW ? 1.f : 1.4426950408889634f;  // (RAW: the logit itself, no log2 domain)
+          const float A0 = (yl0 * n00 + yl1 * n10) * dom;
+          const float A1 = (yl0 * n01 + yl1 * n11) * dom;
           float s0 = 0.f, s1 = 0.f;
           // one 16-byte column record + one 8-byte pixel record per step, the next step's pair requested before this one is used
           int4 xt_n = sXT[x0];
@@ -181,8 +187,12 @@ __device__ __forceinline__ void upsample_gather(Term term, const float* __restri
             const int lab = sc(ll.x);
             if (term.skip(lab)) continue;
             const float xl0 = __int_as_float(sc(xt.z)), xl1 = __int_as_float(sc(xt.w));
-            const float ls = __int_as_float(sc(ll.y));
-            const float prob = __builtin_amdgcn_exp2f(fmaf(xl1, A1, fmaf(xl0, A0, -ls)));
+            float prob;
+            if constexpr (Term::RAW) prob = fmaf(xl1, A1, xl0 * A0);
+            else {
+              const float ls = __int_as_float(sc(ll.y));
+              prob = __builtin_amdgcn_exp2f(fmaf(xl1, A1, fmaf(xl0, A0, -ls)));
+            }
             const float gq = term.term(prob, c, lab, Term::PLANE ? scf(pl) : 0.f);
             s0 = fmaf(xl0, gq, s0);
             s1 = fmaf(xl1, gq, s1);
@@ -238,7 +248,10 @@ __device__ __forceinline__ void upsample_gather(Term term, const float* __restri
           const int lab = term.stage(p, plane);
           if (term.skip(lab)) continue;
           const float v = yl0 * (xl0 * n00 + xl1 * n01) + yl1 * (xl0 * n10 + xl1 * n11);
-          const float gq = term.term(__expf(v - lse[p]), c, lab, plane);
+          float prob;
+          if constexpr (Term::RAW) prob = v;
+          else prob = __expf(v - lse[p]);
+          const float gq = term.term(prob, c, lab, plane);
           t00 += yl0 * xl0 * gq; t01 += yl0 * xl1 * gq; t10 += yl1 * xl0 * gq; t11 += yl1 * xl1 * gq;
         }
         flush();

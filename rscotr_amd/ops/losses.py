@@ -1,5 +1,6 @@
 """Detection / segmentation loss pieces: box utilities, matching cost, the assignment solvers, focal / box loss sums, the
-fused upsample + cross-entropy (plain, and with class weights / avg_non_ignore / OHEM), the fused upsample + Dice."""
+fused upsample + cross-entropy (plain, and with class weights / avg_non_ignore / OHEM), the fused upsample + Dice / Tversky /
+sigmoid focal."""
 import math
 
 import torch
@@ -370,6 +371,127 @@ def upsample_dice(seg_logit, label, ignore_index=255, smooth=1.0, class_weight=N
     if class_weight is not None and not torch.is_tensor(class_weight):
         class_weight = torch.as_tensor(class_weight, dtype=torch.float32, device=seg_logit.device)
     return _UpsampleDice.apply(seg_logit, label, ignore_index, smooth, class_weight, loss_weight)
+
+
+class _UpsampleTversky(Function):
+    """The fused bilinear upsample + softmax + Tversky loss (rscotr_upsample_tversky_*): the Dice Function's buffers and
+    launches on the second instantiation of its kernels."""
+
+    @staticmethod
+    def forward(ctx, logit, label, ignore_index, alpha, beta, smooth, class_weight, loss_weight):
+        logit, label, cw, B, C, h, w, H, W, lse = _upsample_args(logit, label, class_weight)
+        dev = logit.device
+        coef = torch.empty((B, C, 2), dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        nws = lib.rscotr_upsample_tversky_workspace(B, C)
+        # the logits twice (log-sum-exp, then the sums), labels, lse written and re-read
+        with _Prof('upsample_tversky_fwd', 8 * B * C * h * w + 16 * B * H * W):
+            lib.call('rscotr_upsample_tversky_fwd', logit.data_ptr(), label.data_ptr(), _ptr(cw), lse.data_ptr(), coef.data_ptr(),
+                     loss.data_ptr(), B, C, h, w, H, W, int(ignore_index), float(alpha), float(beta), float(smooth),
+                     float(loss_weight), _WS.get(nws, dev).data_ptr(), nws, _stream())
+        ctx.save_for_backward(logit, label, lse, coef)
+        ctx.ignore = int(ignore_index)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        logit, label, lse, coef = ctx.saved_tensors
+        B, C, h, w = logit.shape
+        H, W = label.shape[-2:]
+        gscale = g_loss.reshape(1).float().contiguous()
+        pix_s = torch.empty_like(lse)
+        dlogit = torch.empty_like(logit)
+        # pre-pass: logits, labels, lse read, S written; gather: logits read, gradient written, labels, lse, S read
+        with _Prof('upsample_tversky_bwd', 12 * B * C * h * w + 32 * B * H * W):
+            lib.call('rscotr_upsample_tversky_bwd', logit.data_ptr(), label.data_ptr(), lse.data_ptr(), coef.data_ptr(),
+                     gscale.data_ptr(), pix_s.data_ptr(), dlogit.data_ptr(), B, C, h, w, H, W, ctx.ignore, _stream())
+        return dlogit, None, None, None, None, None, None, None
+
+
+def upsample_tversky(seg_logit, label, ignore_index=255, alpha=0.3, beta=0.7, smooth=1.0, class_weight=None, loss_weight=1.0):
+    """mmseg 0.28 TverskyLoss as BaseDecodeHead.losses reaches it, fused: bilinear resize (align_corners=False) to the label
+    size, softmax, and per (image, class)
+        TP = sum p t v,  FP = sum p (1 - t) v,  FN = sum (1 - p) t v,
+    t the one-hot of clamp(label, 0, C-1), v = [label != ignore_index] (all three sums masked, unlike Dice's denominator);
+        loss = loss_weight / C * sum_{c != ignore_index} class_weight[c] * mean_b (1 - (TP + smooth) / (TP + alpha FP + beta FN + smooth)).
+    alpha + beta == 1 and smooth > 0 (an all-ignored image would be 0 / 0), else ValueError.  Neither the up-sampled logits nor
+    the probabilities are materialised (rscotr_upsample_tversky_*); bit-reproducible.
+    seg_logit (B,C,h,w), label (B,H,W) int64, class_weight a float tensor / list of C entries or None -> loss 0-d."""
+    if float(alpha) + float(beta) != 1.0:
+        raise ValueError(f'upsample_tversky: alpha + beta must be 1.0, got {alpha} + {beta}')
+    if not float(smooth) > 0:
+        raise ValueError(f'upsample_tversky: smooth must be > 0, got {smooth}')
+    if class_weight is not None and not torch.is_tensor(class_weight):
+        class_weight = torch.as_tensor(class_weight, dtype=torch.float32, device=seg_logit.device)
+    return _UpsampleTversky.apply(seg_logit, label, ignore_index, alpha, beta, smooth, class_weight, loss_weight)
+
+
+class _UpsampleFocal(Function):
+    """The fused bilinear upsample + sigmoid focal loss (rscotr_upsample_focal_*).  Nothing per pixel is saved: backward walks the
+    logits again.  scale (loss_weight, over B*H*W*C for the mean) and the upstream gradient meet in the device scalar grad_scale."""
+
+    @staticmethod
+    def forward(ctx, logit, label, ignore_index, gamma, alpha, alpha_c, class_weight, scale):
+        logit = _f32c(logit)
+        label = label.contiguous()
+        cw = None if class_weight is None else _f32c(class_weight)
+        ac = None if alpha_c is None else _f32c(alpha_c)
+        _chk(logit, label, cw, ac)
+        B, C, h, w = logit.shape
+        H, W = label.shape[-2:]
+        for name, t in (('class_weight', cw), ('alpha', ac)):
+            if t is not None and t.numel() != C:
+                raise ValueError(f'{name} has {t.numel()} entries, the logits have {C} channels')
+        loss = torch.empty(1, dtype=torch.float32, device=logit.device)
+        nws = lib.rscotr_upsample_focal_workspace()
+        # the logits and the labels once
+        with _Prof('upsample_focal_fwd', 4 * B * C * h * w + 8 * B * H * W):
+            lib.call('rscotr_upsample_focal_fwd', logit.data_ptr(), label.data_ptr(), _ptr(ac), _ptr(cw), loss.data_ptr(), B, C, h,
+                     w, H, W, int(ignore_index), float(gamma), float(alpha), float(scale), _WS.get(nws, logit.device).data_ptr(),
+                     nws, _stream())
+        ctx.save_for_backward(logit, label, ac, cw)
+        ctx.opts = (int(ignore_index), float(gamma), float(alpha), float(scale))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        logit, label, ac, cw = ctx.saved_tensors
+        ignore, gamma, alpha, scale = ctx.opts
+        B, C, h, w = logit.shape
+        H, W = label.shape[-2:]
+        gscale = (g_loss * scale).reshape(1).float().contiguous()
+        dlogit = torch.empty_like(logit)
+        # logits read, gradient written, labels read
+        with _Prof('upsample_focal_bwd', 8 * B * C * h * w + 8 * B * H * W):
+            lib.call('rscotr_upsample_focal_bwd', logit.data_ptr(), label.data_ptr(), _ptr(ac), _ptr(cw), gscale.data_ptr(),
+                     dlogit.data_ptr(), B, C, h, w, H, W, ignore, gamma, alpha, _stream())
+        return dlogit, None, None, None, None, None, None, None
+
+
+def upsample_focal(seg_logit, label, ignore_index=255, gamma=2.0, alpha=0.5, class_weight=None, reduction='mean', loss_weight=1.0):
+    """mmseg 0.28 FocalLoss (the sigmoid form, py_sigmoid_focal_loss) as BaseDecodeHead.losses reaches it, fused: bilinear resize
+    (align_corners=False) to the label size, then per pixel and class
+        t = [label == c],  v = [label != ignore_index],  s = sigmoid(u),  q = (1 - s) t + s (1 - t),
+        e = BCE_with_logits(u, t) * (alpha_c t + (1 - alpha_c) (1 - t)) * q^gamma * class_weight[c] * v;
+        reduction='mean': loss_weight * sum e / (B*H*W*C) (ignored pixels count in the divisor);  'sum': loss_weight * sum e.
+    A label outside [0, C) that is not ignore_index has no positive class: the pixel is all-negative (mmseg's F.one_hot would
+    raise there).  gamma >= 0 (0 gives q^0 = 1 everywhere, with a finite gradient); alpha a float, or a tensor / list of C
+    floats; class_weight a float tensor / list of C entries or None.  The up-sampled logits are not materialised
+    (rscotr_upsample_focal_*); stable at any logit magnitude; bit-reproducible.
+    seg_logit (B,C,h,w), label (B,H,W) int64 -> loss 0-d."""
+    if reduction not in ('mean', 'sum'):
+        raise NotImplementedError(f"upsample_focal: reduction={reduction!r} (only 'mean' and 'sum')")
+    alpha_c = None
+    if torch.is_tensor(alpha) or isinstance(alpha, (list, tuple)):
+        alpha_c, alpha = torch.as_tensor(alpha, dtype=torch.float32, device=seg_logit.device), 0.0
+    if not float(gamma) >= 0:
+        raise ValueError(f'upsample_focal: gamma must be >= 0, got {gamma}')
+    if class_weight is not None and not torch.is_tensor(class_weight):
+        class_weight = torch.as_tensor(class_weight, dtype=torch.float32, device=seg_logit.device)
+    B, C = seg_logit.shape[:2]
+    H, W = label.shape[-2:]
+    scale = float(loss_weight) / float(max(B * H * W * C, 1)) if reduction == 'mean' else float(loss_weight)
+    return _UpsampleFocal.apply(seg_logit, label, ignore_index, gamma, alpha, alpha_c, class_weight, scale)
 
 
 class _DetProposals(Function):

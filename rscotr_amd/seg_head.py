@@ -96,6 +96,92 @@ class DiceLoss(nn.Module):
 
 
 @MODELS.register_module()
+class TverskyLoss(nn.Module):
+    """mmseg 0.28 TverskyLoss as the seg head uses it: the options are stored here and applied by the fused kernels
+    (ops.upsample_tversky).  Like DiceLoss, forward swallows the `weight` and `ignore_index` that BaseDecodeHead.losses passes: a
+    pixel sampler's mask and the head's ignore_index do not reach this loss; its OWN ignore_index masks the three sums and skips
+    that channel.  No parameters, no buffers: the state dict keeps the reference's keys."""
+
+    def __init__(self, smooth=1, class_weight=None, loss_weight=1.0, ignore_index=255, alpha=0.3, beta=0.7,
+                 loss_name='loss_tversky'):
+        super().__init__()
+        if alpha + beta != 1.0:
+            raise ValueError(f'TverskyLoss: alpha + beta must be 1.0, got {alpha} + {beta}')
+        if not smooth > 0:
+            raise ValueError(f'TverskyLoss: smooth={smooth!r} (> 0: an all-ignored image would be 0 / 0)')
+        self.smooth, self.alpha, self.beta = float(smooth), float(alpha), float(beta)
+        self.class_weight = _class_weight_list(class_weight)
+        self.loss_weight, self.ignore_index, self.loss_name = float(loss_weight), int(ignore_index), loss_name
+        self._cw = {}
+
+    def weight_on(self, device, num_channels):
+        return _class_weight_on(self, device, num_channels)
+
+    def forward(self, seg_logit, label, **kwargs):
+        """seg_logit (B,C,h,w) at the head's resolution, label (B,H,W) int64 -> loss_weight * tversky (0-d)."""
+        cw = self.weight_on(seg_logit.device, seg_logit.shape[1])
+        return ops.upsample_tversky(seg_logit, label, self.ignore_index, alpha=self.alpha, beta=self.beta, smooth=self.smooth,
+                                    class_weight=cw, loss_weight=self.loss_weight)
+
+
+class FocalLoss(nn.Module):
+    """mmseg 0.28 FocalLoss (the sigmoid form) as the seg head uses it: the options are stored here and applied by the fused
+    kernels (ops.upsample_focal) with the HEAD's ignore_index, as BaseDecodeHead.losses passes it.  alpha: a float or a list of
+    one float per logit channel; class_weight as CrossEntropyLoss takes it.  Not in MODELS: that name is the det head's mmdet
+    holder (det_head.FocalLoss); the seg head resolves its loss_decode entries through _SEG_LOSSES.  No parameters, no buffers."""
+
+    def __init__(self, use_sigmoid=True, gamma=2.0, alpha=0.5, reduction='mean', class_weight=None, loss_weight=1.0,
+                 loss_name='loss_focal'):
+        super().__init__()
+        if not use_sigmoid:
+            raise NotImplementedError('FocalLoss: use_sigmoid=False is not implemented (mmseg supports the sigmoid form only)')
+        if reduction not in ('mean', 'sum'):
+            raise NotImplementedError(f"FocalLoss: reduction={reduction!r} (only 'mean' and 'sum')")
+        if not gamma >= 0:
+            raise ValueError(f'FocalLoss: gamma must be >= 0, got {gamma}')
+        if isinstance(alpha, (list, tuple)):
+            alpha = [float(v) for v in alpha]
+        elif isinstance(alpha, (int, float)) and not isinstance(alpha, bool):
+            alpha = float(alpha)
+        else:
+            raise TypeError(f'FocalLoss: alpha must be a float or a list of floats, got {type(alpha).__name__}')
+        self.gamma, self.alpha, self.reduction = float(gamma), alpha, reduction
+        self.class_weight = _class_weight_list(class_weight)
+        self.loss_weight, self.loss_name = float(loss_weight), loss_name
+        self._cw, self._alpha = {}, {}
+
+    def weight_on(self, device, num_channels):
+        return _class_weight_on(self, device, num_channels)
+
+    def alpha_on(self, device, num_channels):
+        """The scalar alpha, or the per-class list as a tensor on `device` (cached per device), checked against the channels."""
+        if not isinstance(self.alpha, list):
+            return self.alpha
+        if len(self.alpha) != num_channels:
+            raise ValueError(f'alpha has {len(self.alpha)} entries, the logits have {num_channels} channels')
+        t = self._alpha.get(str(device))
+        if t is None:
+            t = self._alpha[str(device)] = torch.tensor(self.alpha, dtype=torch.float32, device=device)
+        return t
+
+    def forward(self, seg_logit, label, ignore_index=255, **kwargs):
+        """seg_logit (B,C,h,w) at the head's resolution, label (B,H,W) int64 -> loss_weight * focal (0-d)."""
+        C = seg_logit.shape[1]
+        return ops.upsample_focal(seg_logit, label, ignore_index, gamma=self.gamma, alpha=self.alpha_on(seg_logit.device, C),
+                                  class_weight=self.weight_on(seg_logit.device, C), reduction=self.reduction,
+                                  loss_weight=self.loss_weight)
+
+
+# the types a seg head's loss_decode entries resolve to (every one but the first as an entry of a list only)
+_SEG_LOSSES = {'CrossEntropyLoss': CrossEntropyLoss, 'DiceLoss': DiceLoss, 'FocalLoss': FocalLoss, 'TverskyLoss': TverskyLoss}
+
+
+def _build_seg_loss(cfg):
+    args = copy.deepcopy(dict(cfg))
+    return _SEG_LOSSES[args.pop('type')](**args)
+
+
+@MODELS.register_module()
 class OHEMPixelSampler:
     """mmseg OHEMPixelSampler with a probability threshold: keep the non-ignored pixels whose label probability is below
     max(thresh, the (min_kept * batch)-th smallest one).  The selection runs on the device inside ops.upsample_ce_weighted."""
@@ -229,19 +315,25 @@ class Mask2FormerHead(nn.Module):
         # a dict or a list of dicts, as mmseg's BaseDecodeHead takes it (mask2former_head.py:85-93); no parameters, no keys
         # The single-dict form stays what it was, one CrossEntropyLoss; a DiceLoss is an entry of a loss_decode LIST (next to a
         # CrossEntropyLoss entry as in mmseg's documented pair, or on its own: [dict(type='DiceLoss')])
+        # FocalLoss and TverskyLoss are list entries like DiceLoss.  The entry types resolve through _SEG_LOSSES: 'FocalLoss' in
+        # MODELS is the det head's holder
         is_list = isinstance(loss_decode, (list, tuple))
         cfgs = list(loss_decode) if is_list else [loss_decode]
-        allowed = ('CrossEntropyLoss', 'DiceLoss') if is_list else ('CrossEntropyLoss',)
+        allowed = tuple(_SEG_LOSSES) if is_list else ('CrossEntropyLoss',)
         for c in cfgs:
             if not isinstance(c, dict) or c.get('type') not in allowed:
                 name = c.get('type') if isinstance(c, dict) else type(c).__name__
-                if name == 'DiceLoss':
-                    raise NotImplementedError("loss_decode type 'DiceLoss' as a single dict: DiceLoss is taken as an entry of a "
-                                              "loss_decode list, e.g. [dict(type='CrossEntropyLoss'), dict(type='DiceLoss')]")
-                raise NotImplementedError(f'loss_decode type {name!r}: the fused seg losses implement CrossEntropyLoss, and DiceLoss '
-                                          'as an entry of a list, only')
-        built = [MODELS.build(c) for c in cfgs]
+                if name in _SEG_LOSSES:
+                    raise NotImplementedError(f"loss_decode type {name!r} as a single dict: {name} is taken as an entry of a "
+                                              f"loss_decode list, e.g. [dict(type='CrossEntropyLoss'), dict(type={name!r})]")
+                raise NotImplementedError(f'loss_decode type {name!r}: the fused seg losses implement CrossEntropyLoss, and DiceLoss, '
+                                          'FocalLoss and TverskyLoss as entries of a list, only')
+        built = [_build_seg_loss(c) for c in cfgs]
         self.loss_decode = nn.ModuleList(built) if isinstance(loss_decode, (list, tuple)) else built[0]
+        if sampler is not None and any(isinstance(ld, FocalLoss) for ld in built):
+            # (mmseg hands the sampler's (B,H,W) weight to a (B*H*W, C) loss and fails there itself)
+            raise NotImplementedError('a pixel sampler with a FocalLoss entry in loss_decode: mmseg cannot apply the sampler\'s '
+                                      'per-pixel weight to the per-class focal loss')
         self.sampler = None
         if sampler is not None:
             if not isinstance(sampler, dict) or sampler.get('type') != 'OHEMPixelSampler':
@@ -334,14 +426,15 @@ class Mask2FormerHead(nn.Module):
         ce = [ld for ld in entries if isinstance(ld, CrossEntropyLoss)]
         if len(ce) == len(entries):
             return self._ce_losses(ce, seg_logit, seg_label)
-        # a list with DiceLoss entries: the cross-entropy entries take the path they take alone; every Dice entry is one fused
-        # call (the sampler's mask and the head's ignore_index do not reach it, as in mmseg); entries of one name add up
+        # a list with DiceLoss / TverskyLoss / FocalLoss entries: the cross-entropy entries take the path they take alone; every
+        # other entry is one fused call (the sampler's mask and the head's ignore_index do not reach a Dice or Tversky entry, as
+        # in mmseg; a Focal entry takes the head's ignore_index); entries of one name add up
         out = self._ce_losses(ce, seg_logit, seg_label) if ce else {}
         acc_seg = out.pop('acc_seg', None)
         label = seg_label.squeeze(1)
         for ld in entries:
-            if isinstance(ld, DiceLoss):
-                loss = ld(seg_logit, label)
+            if isinstance(ld, (DiceLoss, TverskyLoss, FocalLoss)):
+                loss = ld(seg_logit, label, ignore_index=self.ignore_index)
                 out[ld.loss_name] = out[ld.loss_name] + loss if ld.loss_name in out else loss
         if acc_seg is None:  # no cross-entropy entry: mmseg reports the accuracy all the same
             with torch.no_grad():
