@@ -332,7 +332,8 @@ int rscotr_splitk_flush(const int64_t* table, const int32_t* wgmap, int nwg, dou
  * work for the launch-site profiler, rscotr_prof_*; 0 = not stated).  Replaces ~110 short launches per co-training round (torch autograd's per-Linear weight-gradient GEMMs behind
  * mmcv's FFN / MultiheadAttention / MultiScaleDeformableAttention modules).  variant 6: the bf16x6 product on 128 x 128
  * tiles with edge handling (M, N, K multiples of 4); variant 7 (round 5): the fp16 split product (rscotr_gemm_f32_r) on the same
- * tiles — table column 14 = (index of A's value-range word + 1) << 32 | index of B's + 1, both into `amax_base` (required). */
+ * tiles — table column 14 = (index of A's value-range word + 1) << 32 | index of B's + 1, both into `amax_base` (required);
+ * variant 7 needs lda, ldb < 2^26 (its k loop addresses a tile with 32-bit offsets — problems with wider operands belong to variant 6). */
 int rscotr_gemm_dw_group(const int64_t* table, int n, int total_wgs, int variant, double flops,
                          const uint32_t* amax_base, void* stream);
 

@@ -18,6 +18,22 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-fast-math",
          "-Wno-unused-result"]
 # host-only sources (bit-exact fp64 restatements, e.g. the LSAP solver) must not be FMA-contracted
 HOST_FLAGS = ["-ffp-contract=off"]
+# Kernels that fit their register budget with little to spare (csrc/gemm_split_body.h, h3_two_tiles: 246 - 249 of 256 VGPRs at two
+# wavefronts per SIMD): their sources are compiled with the resource-usage remark, and the build fails if one of them spills.
+REMARK_FLAGS = ["-Rpass-analysis=kernel-resource-usage"]
+NO_SCRATCH = {"gemm_h3.hip": ("gemm_h3_128_kernel",), "gemm_group.hip": ("gemm_h3_group_kernel",)}
+
+
+def scratch_report(remarks, names):
+    """{kernel: bytes of scratch per lane} of the kernels whose mangled name holds one of `names`, from hipcc's
+    kernel-resource-usage remarks."""
+    out, cur = {}, None
+    for line in remarks.splitlines():
+        if "Function Name:" in line:
+            cur = line.split("Function Name:")[1].split()[0]
+        elif "ScratchSize [bytes/lane]:" in line and cur is not None and any(n in cur for n in names):
+            out[cur] = int(line.split("ScratchSize [bytes/lane]:")[1].split()[0])
+    return out
 
 
 def _sources():
@@ -65,7 +81,7 @@ def build_library(force=False, verbose=True):
     for src in _sources():
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
-        extra = HOST_FLAGS if src.endswith(".cpp") else []
+        extra = HOST_FLAGS if src.endswith(".cpp") else REMARK_FLAGS if os.path.basename(src) in NO_SCRATCH else []
         # per-object stamp: a source whose text, headers and flags are unchanged keeps its object
         with open(src, "rb") as fh:
             odig = hashlib.sha256(fh.read() + hdr.digest() + " ".join(FLAGS + extra).encode()).hexdigest()
@@ -84,6 +100,14 @@ def build_library(force=False, verbose=True):
         if p.returncode != 0:
             os.remove(os.path.join(objdir, os.path.basename(src) + ".o.stamp"))
             raise RuntimeError(f"hipcc failed on {src}:\n{out.decode()}")
+        names = NO_SCRATCH.get(os.path.basename(src))
+        if names:
+            report = scratch_report(out.decode(), names)
+            spilled = {k: v for k, v in report.items() if v}
+            if not report or spilled:
+                os.remove(os.path.join(objdir, os.path.basename(src) + ".o.stamp"))
+                raise RuntimeError(f"{src}: kernels that must not use scratch do (bytes per lane: {spilled}), or no resource-usage "
+                                   f"remark was found for {names}: see h3_two_tiles in csrc/gemm_split_body.h")
     cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-ldl", "-o", LIB]
     if verbose:
         print("[rscotr build]", " ".join(cmd), flush=True)

@@ -101,12 +101,23 @@ __device__ __forceinline__ void range_mark(unsigned* slot, int i) {
 
 // (lane l holds sub-word l % kAmaxPlanes, loaded by the caller as early as it likes) -> the bit pattern of 2^e, e = the binade of
 // the tensor's maximum (0 for a word nobody marked: an all-zero tensor); wave-uniform
+// (the two ends of the fold: byte index + 1 of the highest byte set in sub-word `sub`, 0 for none; and the pattern of its binade)
+__device__ __forceinline__ int amax_fold_code(unsigned v, int sub) { return v ? 4 * sub + ((31 - __clz((int)v)) >> 3) + 1 : 0; }
+__device__ __forceinline__ unsigned amax_fold_bits(int c) { return c ? (unsigned)(kRangeExpLo + c - 1) << 23 : 0u; }
 __device__ __forceinline__ unsigned amax_fold(unsigned v) {
-  int c = v ? 4 * (int)(threadIdx.x & (kAmaxPlanes - 1)) + ((31 - __clz((int)v)) >> 3) + 1 : 0;  // byte index + 1
+  int c = amax_fold_code(v, (int)(threadIdx.x & (kAmaxPlanes - 1)));
 #pragma unroll
   for (int o = kAmaxPlanes / 2; o > 0; o >>= 1) c = max(c, __shfl_xor(c, o, 64));
-  c = __builtin_amdgcn_readfirstlane(c);
-  return c ? (unsigned)(kRangeExpLo + c - 1) << 23 : 0u;
+  return amax_fold_bits(__builtin_amdgcn_readfirstlane(c));
+}
+// amax_fold with the caller's lane index (the wavefront's: lane % kAmaxPlanes = threadIdx.x % kAmaxPlanes).  For a kernel short of
+// registers: given a lane index behind an empty asm, the partners' shuffle addresses are this call's own and do not stay in
+// registers until amax_commit, which folds over the same partners, at the end of the kernel (csrc/gemm_split_body.h).
+__device__ __forceinline__ unsigned amax_fold_lane(unsigned v, int lane) {
+  int c = amax_fold_code(v, lane & (kAmaxPlanes - 1));
+#pragma unroll
+  for (int o = kAmaxPlanes / 2; o > 0; o >>= 1) c = max(c, __builtin_amdgcn_ds_bpermute((lane ^ o) << 2, c));
+  return amax_fold_bits(__builtin_amdgcn_readfirstlane(c));
 }
 __device__ __forceinline__ unsigned amax_read(const unsigned* word) {
   return amax_fold(word[(long)(threadIdx.x & (kAmaxPlanes - 1)) * kAmaxStride]);

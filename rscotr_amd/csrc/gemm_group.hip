@@ -19,7 +19,8 @@ constexpr size_t GROUP_LDS_BYTES = 4 * (size_t)bf16x6_lds_words<128, 128, true, 
 // workgroups (measured: 950 -> 1500 us for the launch).  (Variants 2 / 3 / 4 of rounds 3-4 — interior-only 128 x 128, 64 x 64
 // pipelined, fp32 on 128 x 128 — lost every A/B to variant 6 and left the library in round 5.)
 // VAR 7 (round 5): the fp16 split product on the 128 x 128 edge body; table column 14 = (slot of A + 1) << 32 | slot of B + 1,
-// indices into `amax_base` (the value-range words of the two operands).
+// indices into `amax_base` (the value-range words of the two operands); lda, ldb < 2^26 (the two-tile loop of the body addresses
+// a tile with 32-bit offsets: the table's builder, ops/deferred.py, sends wider problems to variant 6).
 template <int VAR>
 __device__ __forceinline__ void gemm_group_dispatch(const int64_t* __restrict__ table, int n, const unsigned* __restrict__ amax_base) {
   extern __shared__ __attribute__((aligned(16))) float gemm_smem[];

@@ -12,10 +12,11 @@ __global__ __launch_bounds__(256, OCC) void gemm_h3_kernel(GemmParams p) {
 }
 // 128 x 128 tiles: two accumulator sets are 128 registers; held to two wavefronts per SIMD (256 registers in all) so that
 // two workgroups per CU cover each other's staging phases in the one-stage loop
-template <bool AKM, bool BKM, bool EDGE = false>
+// ONESET: the one-set loop also where the body would alternate two register sets (both operands k-major; h3_two_tiles)
+template <bool AKM, bool BKM, bool EDGE = false, bool ONESET = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_h3_128_kernel(GemmParams p) {
   __shared__ __attribute__((aligned(16))) unsigned lds[bf16x6_lds_words<128, 128, AKM, BKM, 0, true>()];
-  gemm_bf16x6_body<128, 128, AKM, BKM, 0, false, EDGE, true>(p, blockIdx.x, gridDim.x, lds);
+  gemm_bf16x6_body<128, 128, AKM, BKM, 0, false, EDGE, true, false, ONESET>(p, blockIdx.x, gridDim.x, lds);
 }
 
 void launch_h3(const GemmParams& p, const GemmPlan& pl, hipStream_t s) {
@@ -28,7 +29,9 @@ void launch_h3(const GemmParams& p, const GemmPlan& pl, hipStream_t s) {
       constexpr int BM = decltype(bm)::value, PIPE = decltype(pipe)::value;
       constexpr bool EDGE = decltype(edge)::value, AK = decltype(ak)::value, BK = decltype(bk)::value;
       if constexpr (BM == 128) {
-        gemm_h3_128_kernel<AK, BK, EDGE><<<dim3(pl.nwg), 256, 0, s>>>(p);
+        // (the two-set loop of the k-major layout addresses a tile with 32-bit offsets: SplitOperand::thread_offset)
+        if (AK && BK && (p.lda >= (1 << 26) || p.ldb >= (1 << 26))) gemm_h3_128_kernel<AK, BK, EDGE, AK && BK><<<dim3(pl.nwg), 256, 0, s>>>(p);
+        else gemm_h3_128_kernel<AK, BK, EDGE><<<dim3(pl.nwg), 256, 0, s>>>(p);
       } else if (PIPE == 2 && !EDGE && !AK) {
         // (the interior pipelined 64 x 64 kernels with a row-major A: the 128-register instantiations, four workgroups per CU —
         // 33.84 against 34.00 ms per round, bit-identical results.  A plain `if`: their OCC = 1 forms stay instantiated)

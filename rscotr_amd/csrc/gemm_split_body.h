@@ -132,6 +132,34 @@ struct SplitOperand {
       }
     }
   }
+  // k-major: the reads of load<EDGE, true>() as BUFFER loads.  One descriptor per read, built from uniform values in scalar
+  // registers: it starts at the first k row of the read's item (k0 + 16 i + 0 | 1, for R = 128) and ends with row klim - 1, so a
+  // row at or past klim is out of its range and reads as zeros — the zeros of load() without a select behind the load.  What
+  // differs between threads is ONE 32-bit byte offset, the same for every read and every tile (thread_offset: the thread's k-pair
+  // row inside the item and its four columns, clamped to rlast in the edge form): no 64-bit address per read in vector
+  // registers.  ld < 2^26, so that the offset (< 15 rows + 1) fits 32 bits: launch_h3 sends wider operands to the one-set
+  // kernel, the grouped launch's table builder (ops/deferred.py) to variant 6.
+  __device__ __forceinline__ unsigned thread_offset(int ld, int row0, int tid, bool edge, int rlast) const {
+    static_assert(!KM || ITEMS % 256 == 0, "whole items per thread");
+    const int col = row0 + (tid % (R / 4)) * 4;
+    return 4u * (unsigned)(2 * (tid / (R / 4)) * ld + (edge ? min(col, rlast) : col));
+  }
+  static __device__ __forceinline__ float4 load_row(const float* P, int ld, int krow, int klim, unsigned off) {
+    typedef unsigned vec4u __attribute__((ext_vector_type(4)));
+    const long left = 4l * ld * max(klim - krow, 0);  // bytes up to the end of row klim - 1
+    const __amdgpu_buffer_rsrc_t d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P + (long)krow * ld), 0,
+                                                                        (int)(unsigned)min(left, 0xffffffffl), 0x00020000);
+    const vec4u t = __builtin_amdgcn_raw_buffer_load_b128(d, (int)off, 0, 0);
+    return make_float4(__uint_as_float(t.x), __uint_as_float(t.y), __uint_as_float(t.z), __uint_as_float(t.w));
+  }
+  __device__ __forceinline__ void load_rows(const float* __restrict__ P, int ld, int k0, int klim, unsigned off) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int krow = k0 + i * (2 * 256 / (R / 4));
+      v[i] = load_row(P, ld, krow, klim, off);
+      w[i] = load_row(P, ld, krow + 1, klim, off);
+    }
+  }
   // k-major only: row k of the staged tile times ks[k / per]
   __device__ __forceinline__ void scale_k(const float* __restrict__ ks, int per, int k0, int tid, int klast = 0x7ffffffe) {
 #pragma unroll
@@ -143,6 +171,37 @@ struct SplitOperand {
         v[i].x *= f0; v[i].y *= f0; v[i].z *= f0; v[i].w *= f0;
         w[i].x *= f1; w[i].y *= f1; w[i].z *= f1; w[i].w *= f1;
       }
+    }
+  }
+  // scale_k in two halves, R = 128: the factors are REQUESTED ahead and applied when the tile is staged — the same products as
+  // scale_k, but no wait for the tile at the place of its request.  A wavefront stages four consecutive k rows per item (its two
+  // half-waves one k pair each), so its factors are uniform: 4 NV SCALAR loads (f in scalar registers, the constant address
+  // space: the vector says the same for the whole launch; their counter is not the operand tiles'), one division per item —
+  // the next rows' quotients follow by counting.  wave: the wavefront's index, uniform (readfirstlane).
+  __device__ __forceinline__ void scale_k_fetch(const float* __restrict__ ks, int per, int k0, int wave, int klast, float (&f)[4 * NV]) const {
+    static_assert(!KM || R == 128, "two k pairs per wavefront");
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int kb = k0 + 4 * wave + i * (2 * 256 / (R / 4));
+      int k = min(kb, klast), q = k / per, r = k - q * per;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int kn = min(kb + j, klast);
+        if (kn != k) {
+          k = kn;
+          if (++r == per) { r = 0; ++q; }
+        }
+        f[4 * i + j] = *(const __attribute__((address_space(4))) float*)(ks + q);
+      }
+    }
+  }
+  __device__ __forceinline__ void scale_k_apply(const float (&f)[4 * NV], int tid) {
+    const bool hi = (tid / (R / 4)) & 1;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const float f0 = hi ? f[4 * i + 2] : f[4 * i], f1 = hi ? f[4 * i + 3] : f[4 * i + 1];
+      v[i].x *= f0; v[i].y *= f0; v[i].z *= f0; v[i].w *= f0;
+      w[i].x *= f1; w[i].y *= f1; w[i].z *= f1; w[i].w *= f1;
     }
   }
   // k-major only: running sums over k of the four rows this thread stages (r4 is the same for all its items: 256 is a
@@ -253,6 +312,18 @@ __device__ const float bf16x6_one = 1.f;
 template <int PIPE> constexpr int bf16x6_bk() { return PIPE == 2 ? 32 : PIPE == 0 ? X6_BK0 : 16; }
 constexpr int X6_D2 = 2, H3_VPM = 8, H3_DPM = 2;
 template <int PIPE> constexpr int bf16x6_depth() { return PIPE == 2 ? X6_D2 : 1; }
+// The one-stage loop of the 128 x 128 fp16 split body with two alternating register sets — EVERY OTHER tile two deep in flight
+// as compiled today (see the loop's known shortfall) —, for the weight-gradient layout — both operands k-major: gemm_h3_128_kernel<true, true, *> and variant 7 of the grouped
+// launch.  Those launches wait on memory: two workgroups of four wavefronts per CU, and with one register set a tile is requested
+// one barrier and one MFMA phase before it is needed.  (The other layouts of gemm_h3_128_kernel stay on the one-set loop: with the
+// row-major stager <true, false, *> and <false, true, true> do not fit 256 registers without scratch; <false, false, *> and
+// <false, true, false> fit, but no launch of theirs was measured.  profiles/README.md, "two register sets".)
+// REGISTERS ARE TIGHT: 246 / 248 / 249 of 256 with hipcc of ROCm 7.2, 7 - 10 to spare, held by the empty asm statements below.  A
+// compiler update or an edit nearby can push the three kernels into scratch, which costs more than the loop gains: rscotr_amd/build.py
+// compiles gemm_h3.hip and gemm_group.hip with the resource-usage remark and FAILS the build if one of them reports scratch.
+// ONESET: the caller wants the one-set loop (a leading dimension of 2^26 or more: thread_offset is 32 bits).
+template <int BM, int BN, bool AKM, bool BKM, int PIPE, bool EDGE, bool H16>
+constexpr bool h3_two_tiles() { return H16 && PIPE == 0 && BM == 128 && BN == 128 && AKM && BKM; }
 
 template <int BM, int BN, bool AKM, bool BKM, int PIPE, bool H16 = false>
 constexpr int bf16x6_lds_words() {
@@ -264,9 +335,10 @@ constexpr int bf16x6_lds_words() {
 // lds: bf16x6_lds_words() dwords, 16-byte aligned.
 // H16: the fp16 split product (split_pair_h above): operands scaled by powers of two from p.amax_a / p.amax_b (both
 // required), three MFMAs per 16 k into two accumulator sets.
-template <int BM, int BN, bool AKM, bool BKM, int PIPE, bool SLAB, bool EDGE = false, bool H16 = false, bool BPL = false>
+template <int BM, int BN, bool AKM, bool BKM, int PIPE, bool SLAB, bool EDGE = false, bool H16 = false, bool BPL = false, bool ONESET = false>
 __device__ __forceinline__ void gemm_bf16x6_body(GemmParams& p, const int bx, const int gx, unsigned* lds) {
-  constexpr int NPL = H16 ? 2 : 3, SBK = bf16x6_bk<PIPE>(), D = bf16x6_depth<PIPE>();
+  constexpr bool TWO = !ONESET && h3_two_tiles<BM, BN, AKM, BKM, PIPE, EDGE, H16>();
+  constexpr int NPL = H16 ? 2 : 3, SBK = bf16x6_bk<PIPE>(), D = TWO ? 2 : bf16x6_depth<PIPE>();
   constexpr int MT = BM / 64, NT = BN / 64;
   using OA = SplitOperand<BM, AKM, NPL, SBK, H16>;
   static_assert(!BPL || (H16 && !BKM && !EDGE && PIPE == 2), "B from planes: the interior pipelined fp16 kernel");
@@ -283,7 +355,14 @@ __device__ __forceinline__ void gemm_bf16x6_body(GemmParams& p, const int bx, co
   }
   auto h3_scales = [&]() {
     if constexpr (H16) {
-      const int ea = h3_scale_exp(amax_fold(ra)), eb = h3_scale_exp(amax_fold(rb));
+      if constexpr (TWO) {  // (amax_fold_lane, common.h: the shuffle addresses do not stay in registers through the loop)
+        int ln = (int)__lane_id();
+        asm volatile("" : "+v"(ln));
+        ra = amax_fold_lane(ra, ln); rb = amax_fold_lane(rb, ln);
+      } else {
+        ra = amax_fold(ra); rb = amax_fold(rb);
+      }
+      const int ea = h3_scale_exp(ra), eb = h3_scale_exp(rb);
       ha.sc = __uint_as_float((unsigned)ea << 23); ha.sc2 = __uint_as_float((unsigned)(ea + 11) << 23);
       hb.sc = __uint_as_float((unsigned)eb << 23); hb.sc2 = __uint_as_float((unsigned)(eb + 11) << 23);
       inva = __uint_as_float((unsigned)(254 - ea) << 23); invb = __uint_as_float((unsigned)(254 - eb) << 23);
@@ -292,8 +371,8 @@ __device__ __forceinline__ void gemm_bf16x6_body(GemmParams& p, const int bx, co
   constexpr int NBUF = PIPE ? 2 : 1;
   unsigned* sA[2] = {lds, lds + (NBUF - 1) * OA::WORDS};
   unsigned* sB[2] = {lds + NBUF * OA::WORDS, lds + NBUF * OA::WORDS + (NBUF - 1) * OB::WORDS};
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
+  int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;  // (not const: the two-tile loop derives them again behind itself)
+  int wm = wave >> 1, wn = wave & 1;
   const int tiles_n = EDGE ? (p.N + BN - 1) / BN : p.N / BN;
   const int alast = EDGE ? (AKM ? p.M - 4 : p.M - 1) : 0, blast = EDGE ? (BKM ? p.N - 4 : p.N - 1) : 0;
   int tile, split = 0;
@@ -331,7 +410,7 @@ __device__ __forceinline__ void gemm_bf16x6_body(GemmParams& p, const int bx, co
   OB& lb = lbs[0];
   const bool do_rs = AKM && p.rowsum && n0 == 0;  // bias gradient riding the dW contraction (tile column 0)
   float4 rs = make_float4(0.f, 0.f, 0.f, 0.f);
-  const int fr = lane & 31, g = lane >> 5;
+  int fr = lane & 31, g = lane >> 5;
   auto fetch = [&](int t) {
     la.template load<EDGE>(p.A, p.lda, m0, kbeg + t * SBK, tid, alast, p.K);
     lb.template load<EDGE>(p.B, p.ldb, n0, kbeg + t * SBK, tid, blast, p.K);
@@ -343,13 +422,18 @@ __device__ __forceinline__ void gemm_bf16x6_body(GemmParams& p, const int bx, co
     lb.store(b_s, tid, hb);
   };
   auto mma = [&](const unsigned* a_s, const unsigned* b_s) {
+    int ra0 = wm * (BM / 2) + fr, rb0 = wn * (BN / 2) + fr;
+    // (two tiles in flight: the fragment rows pass through an empty asm in every step, so that the sixteen LDS addresses of the
+    // fragment reads — per operand, plane, substep and row half — are offsets of one register each inside the step and not
+    // sixteen loop invariants held in registers across the loop: the second register set needs that room)
+    if constexpr (TWO) asm volatile("" : "+v"(ra0), "+v"(rb0));
 #pragma unroll
     for (int ks = 0; ks < SBK / 16; ++ks) {
       bf16x8 af[MT][3], bf[NT][3];
 #pragma unroll
-      for (int i = 0; i < MT; ++i) OA::frag(a_s, wm * (BM / 2) + i * 32 + fr, g, ks, af[i]);
+      for (int i = 0; i < MT; ++i) OA::frag(a_s, ra0 + i * 32, g, ks, af[i]);
 #pragma unroll
-      for (int j = 0; j < NT; ++j) OB::frag(b_s, wn * (BN / 2) + j * 32 + fr, g, ks, bf[j]);
+      for (int j = 0; j < NT; ++j) OB::frag(b_s, rb0 + j * 32, g, ks, bf[j]);
       if constexpr (H16) {
         // l h, h l into the second accumulator set, h h into the first; term-major as below
 #pragma unroll
@@ -439,6 +523,73 @@ __device__ __forceinline__ void gemm_bf16x6_body(GemmParams& p, const int bx, co
       }
       __syncthreads();
     }
+  } else if constexpr (TWO) {
+    // The one-stage loop with tile t + 2 requested before tile t + 1 is staged: two register sets that alternate (static indices:
+    // two steps per round), one LDS stage, the same barriers.  Nothing READS a loaded register before the staging of its tile:
+    // the zeros past K of the edge form come with the buffer loads themselves (load_rows), and the per-sample k scaling is
+    // applied at staging from factors requested one step ahead (scalar loads into one set of scalar registers: scale_k_fetch) —
+    // in the one-set loop below a select or a product right behind the loads makes the wavefront wait for the tile where it is
+    // requested.  Values, their order into the row sums and the MFMA sequence are those of that loop, bit for bit.  Requests
+    // are NOT predicated (a request under a branch leaves the set as a merge of old and new registers, which the compiler
+    // resolves with copies — and waits — behind the loads): the descriptors end with the k-slice, so a request past it moves no
+    // data.
+    // Registers: 128 accumulators + 64 for the two sets leave 64 for everything else; the empty asm statements (mma, h3_scales,
+    // behind the loop) keep loop invariants out of them that are cheaper to derive again (246 - 249 registers, no scratch).
+    // Known shortfall (profiles/README.md): the register allocator still moves four registers of set 1 at the end of a round, behind
+    // their loads, so the odd tiles are waited for there — one MFMA phase after their request, as in the one-set loop.
+    float kf[4 * OA::NV];
+    const unsigned offa = la.thread_offset(p.lda, m0, tid, EDGE, alast);
+    const unsigned offb = lb.thread_offset(p.ldb, n0, tid, EDGE, blast);
+    const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
+    auto factors = [&](int t) {
+      if (p.kscale) la.scale_k_fetch(p.kscale, p.krows_per, kbeg + t * SBK, wave_u, klast, kf);
+    };
+    auto fetch2 = [&](auto set, int t) {
+      constexpr int S = decltype(set)::value;
+      // (readfirstlane: k0 is uniform anyway; behind the intrinsic the addresses are no function of the loop counter that the
+      // compiler could turn into one running 64-bit pointer per read — sixteen register pairs for the two sets)
+      const int k0 = __builtin_amdgcn_readfirstlane(kbeg + t * SBK);
+      las[S].load_rows(p.A, p.lda, k0, kend, offa);
+      lbs[S].load_rows(p.B, p.ldb, k0, kend, offb);
+    };
+    auto stage2 = [&](auto set) {
+      constexpr int S = decltype(set)::value;
+      // (the set passes through an empty asm: no use of a loaded register — the compiler pairs them up for the packed conversions
+      // with moves — may be scheduled in front of this point, back into the step that requested the tile)
+#pragma unroll
+      for (int i = 0; i < OA::NV; ++i) {
+        asm volatile("" : "+v"(las[S].v[i].x), "+v"(las[S].v[i].y), "+v"(las[S].v[i].z), "+v"(las[S].v[i].w));
+        asm volatile("" : "+v"(las[S].w[i].x), "+v"(las[S].w[i].y), "+v"(las[S].w[i].z), "+v"(las[S].w[i].w));
+        asm volatile("" : "+v"(lbs[S].v[i].x), "+v"(lbs[S].v[i].y), "+v"(lbs[S].v[i].z), "+v"(lbs[S].v[i].w));
+        asm volatile("" : "+v"(lbs[S].w[i].x), "+v"(lbs[S].w[i].y), "+v"(lbs[S].w[i].z), "+v"(lbs[S].w[i].w));
+      }
+      if (p.kscale) las[S].scale_k_apply(kf, tid);
+      if (do_rs) las[S].accum(rs, tid);
+      las[S].store(sA[0], tid, ha);
+      lbs[S].store(sB[0], tid, hb);
+    };
+    constexpr std::integral_constant<int, 0> s0{};
+    constexpr std::integral_constant<int, 1> s1{};
+    factors(0);
+    fetch2(s0, 0);
+    fetch2(s1, 1);
+    h3_scales();
+    for (int t = 0; t < nk; t += 2) {
+      __syncthreads();  // the previous tile has been consumed
+      stage2(s0);
+      if (t + 1 < nk) factors(t + 1);
+      fetch2(s0, t + 2);
+      __syncthreads();
+      mma(sA[0], sB[0]);
+      if (t + 1 < nk) {
+        __syncthreads();
+        stage2(s1);
+        if (t + 2 < nk) factors(t + 2);
+        fetch2(s1, t + 3);
+        __syncthreads();
+        mma(sA[0], sB[0]);
+      }
+    }
   } else {
     fetch(0);
     h3_scales();
@@ -451,6 +602,12 @@ __device__ __forceinline__ void gemm_bf16x6_body(GemmParams& p, const int bx, co
     }
   }
 
+  if constexpr (TWO) {
+    // what the epilogue derives from the thread index (output rows and columns, the row-sum fold's addresses) is derived AFTER the
+    // loop: computed in front of it, a dozen values would sit in registers through the loop, which has none to spare
+    asm volatile("" : "+v"(tid));
+    lane = tid & 63; wave = tid >> 6; wm = wave >> 1; wn = wave & 1; fr = lane & 31; g = lane >> 5;
+  }
   if (AKM && do_rs) {  // thread t summed rows (t % (BM/4)) * 4 .. + 3 over the k-pairs it staged: fold the 8 k-lanes
     __syncthreads();
     constexpr int KL = 256 / (BM / 4) < OA::KP ? 256 / (BM / 4) : OA::KP;  // distinct k-lanes among the threads (item i of a

@@ -116,8 +116,9 @@ class _DeferredCombine:
         def kind(p):
             if not (self.split_member(p.M, p.N, p.K) and p.lda % 4 == 0 and p.ldb % 4 == 0 and p.a % 16 == 0 and p.b % 16 == 0):
                 return 0
-            # with the value range of both operands: the same body as the fp16 split product
-            return 7 if p.range_a and p.range_b and RANGES.enabled else 6
+            # with the value range of both operands: the same body as the fp16 split product (whose k loop addresses a tile with
+            # 32-bit offsets: leading dimensions below 2^26, csrc/gemm_split_body.h thread_offset)
+            return 7 if p.range_a and p.range_b and RANGES.enabled and max(p.lda, p.ldb) < 1 << 26 else 6
 
         def row(m, first):
             """Table row of member m (None: a bundle's padding) whose bundle starts at workgroup `first`."""
