@@ -33,7 +33,8 @@ extern "C" {
  * evaluation entries since — seg_predict / seg_areas, det_decode / det_match, seg_predict_tta, seg_predict_slide — are additive and change no
  * argument list, so they keep 11: a library without them fails to bind by name; the seg head's scheme-1 entries rscotr_seg_mix_* and
  * the det input chain rscotr_img_aug_chain_u8 likewise, and the Dice, Tversky and focal seg losses
- * rscotr_upsample_dice_* / rscotr_upsample_tversky_* / rscotr_upsample_focal_*).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
+ * rscotr_upsample_dice_* / rscotr_upsample_tversky_* / rscotr_upsample_focal_*, and the rotation input entries
+ * rscotr_img_aug_rot_u8 / rscotr_seg_label_rot_u8).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
  * its first call (rscotr_amd/_lib.py does) — a stale .so would take a stream handle for a pointer. */
 #define RSCOTR_ABI_VERSION 11
 int rscotr_version(void);
@@ -777,13 +778,15 @@ int rscotr_comm_destroy(void* comm);
 
 /* ---- device-side input pipeline --------------------------------------------------------
  * One launch turns a batch of ragged decoded uint8 images into the collated network input: crop window ->
- * horizontal flip -> BGR->RGB + (x - mean) / std -> zero pad to (Hout, Wout) -> (B, 3, Hout, Wout) float32.
+ * flip -> BGR->RGB + (x - mean) / std -> zero pad to (Hout, Wout) -> (B, 3, Hout, Wout) float32.
  * Replaces the per-sample pipeline tail + collate of the reference's dataset configs (mmcv imflip / imnormalize /
  * impad, ImageToTensor / DefaultFormatBundle): configs/_base_/cls/resisc_swin_224.py:14,36-38,
  * configs/_base_/det/dior.py:15-19, configs/_base_/seg/potsdam_IRRG_all.py:12-19.
  * src: device byte buffer holding every sample's HWC (3 bytes per pixel) image; meta: device (B, 10) int64 rows
- * {byte offset, H, W, row stride in bytes, crop x0, crop y0, crop w, crop h, flip (0/1), reserved}; the crop window must
+ * {byte offset, H, W, row stride in bytes, crop x0, crop y0, crop w, crop h, flip, reserved}; the crop window must
  * lie inside the image and crop w / h <= Wout / Hout (caller-checked: the entry cannot read device memory).
+ * flip, here and in the meta rows of every entry of this section, is a bit set (mmcv imflip on the cropped window): bit 0
+ * mirrors x ('horizontal': the former 0 / 1, results unchanged), bit 1 mirrors y ('vertical'), 3 = both (mmdet 'diagonal').
  * mean3 / std3: HOST pointers to 3 floats each, in output-channel order (RGB when to_rgb).
  * rscotr_seg_label_prep_u8: the same geometry for a 1-byte-per-pixel label map -> (B, 1, Hout, Wout) int64, padded
  * with pad_val (seg_pad_val); reduce_zero_label applies mmseg LoadAnnotations' 0 -> 255, l -> l - 1. */
@@ -821,7 +824,8 @@ int rscotr_seg_label_aug_u8(const uint8_t* src, const int64_t* meta, const int32
  * layout, read as {byte offset, H, W, row stride in bytes, frame-1 window w, h, 0, stage-1 x-table offset, y-table offset,
  * x taps K, y taps K, stage-1 resample mode (0 nearest | 1 bilinear), stage-2 x-table offset, stage-2 y-table offset, out w,
  * out h, reserved x 4}.  Stage-1 entries are rscotr_img_aug_u8's and describe the crop window of frame 1 (entry j = window
- * coordinate j; a flip in front of the first resize is mirrored into the x entries by the host: the kernel flips nothing).
+ * coordinate j; a flip in front of the first resize is mirrored into the x entries, a vertical or diagonal one also into the
+ * y entries, by the host: the kernel flips nothing).
  * Stage-2 entries have 4 words {first window coordinate of frame 1, taps n <= 2, w0, w1} (OpenCV fixed-point bilinear of the
  * window, 11-bit weights; the final window's offset folded in; one tap of weight 2048 = read as is, which is how a sample with
  * one resize rides in the same launch).  out = clamp((sum wy * sum wx * f1 + 2^21) >> 22) with every f1 the uint8 pixel stage 1
@@ -830,6 +834,29 @@ int rscotr_seg_label_aug_u8(const uint8_t* src, const int64_t* meta, const int32
  * Hout (caller-checked: the entry cannot read device memory). */
 int rscotr_img_aug_chain_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, float* out, int B, int Hout,
                             int Wout, const float* mean3, const float* std3, int to_rgb, void* stream);
+
+/* rscotr_img_aug_rot_u8: rscotr_img_aug_u8 with mmseg RandomRotate (mmcv.imrotate = cv2.warpAffine, INTER_LINEAR, borderValue =
+ * pad_val, auto_bound=False) between the flipped window and the colour stages, in ONE launch, the uint8 window never stored
+ * (additive entries: the ABI revision is unchanged).  src, meta, tables, params and the tail of the argument list are
+ * rscotr_img_aug_u8's.  rot: device (B, 4) int32 rows {warp table offset (int32 elements into `warp`; 0 = the sample is not
+ * rotated and its pixels equal rscotr_img_aug_u8's bit for bit), pad B, pad G, pad R}.  warp: device int32, per rotated sample
+ * {adelta[out w], bdelta[out w], X0[out h], Y0[out h]} of cv2.warpAffine's fixed point in WINDOW coordinates, the layout of
+ * rscotr_randaug_u8's (AB_SCALE 1024, the inverse matrix in float64, round_delta 16 folded into X0 / Y0), built by the host.
+ * Per output pixel: X = (X0[y] + adelta[x]) >> 5, sx = X >> 5, ax = X & 31 (y alike); taps (sy .. sy + 1) x (sx .. sx + 1) with
+ * the weights (32 - ay | ay) * (32 - ax | ax) * 32 (exact integers that sum to 32768); a tap inside the window is the uint8
+ * pixel rscotr_img_aug_u8 makes there (un-flipped, resampled through the entries), a tap outside is the pad colour;
+ * out = (sum w * p + 2^14) >> 15; then photometric -> erasing -> normalize -> pad.  Integer up to the normalize.
+ * rscotr_seg_label_rot_u8: the same geometry, cv2 INTER_NEAREST (round_delta 512 folded in, sx = X >> 10) for the label map of
+ * rscotr_seg_label_aug_u8 (meta / tables of that entry).  rot: device (B, 4) int32 rows {warp table offset (0 = not rotated),
+ * seg_pad_val of the rotation, reserved x 2}: inside the window the raw label is read and reduce_zero_label applies; outside
+ * it the value is seg_pad_val as given, NOT reduced (mmseg reduces at load time, before the fill); outside the window's
+ * (out w, out h) it is pad_val.  Every warp offset + 2 * (out w + out h) must lie inside `warp` (caller-checked). */
+int rscotr_img_aug_rot_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, const float* params,
+                          const int32_t* rot, const int32_t* warp, float* out, int B, int Hout, int Wout, const float* mean3,
+                          const float* std3, int to_rgb, void* stream);
+int rscotr_seg_label_rot_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, const int32_t* rot,
+                            const int32_t* warp, int64_t* out, int B, int Hout, int Wout, int reduce_zero_label, int pad_val,
+                            void* stream);
 
 /* ---- RandAugment on the device ---------------------------------------------------------------------------------------------
  * Replaces mmcls RandAugment(policies=rand_increasing_policies, num_policies=2, total_level=10, magnitude_level=9,

@@ -1,4 +1,4 @@
-// Device-side input pipeline for gfx950: crop window -> horizontal flip -> BGR->RGB + (x - mean) / std -> pad ->
+// Device-side input pipeline for gfx950: crop window -> flip (x, y or both) -> BGR->RGB + (x - mean) / std -> pad ->
 // HWC uint8 to CHW float32 -> collate, one launch for a whole batch of ragged decoded images.
 //
 // Replaces, per sample on a CPU worker and then `collate`, the pipeline tail of the reference's dataset configs
@@ -9,7 +9,10 @@
 // (mmcv.imflip / imnormalize / impad, mmseg LoadAnnotations; the un-vendored mm* pipelines run these in NumPy/OpenCV
 // on float32 copies of the image: ~6 passes over the pixels per sample plus the collate copy).  Resizing, the
 // photometric and the erasing steps are the second pair of entries below (rscotr_img_aug_u8 / rscotr_seg_label_aug_u8);
-// RandAugment is rscotr_img_frames_u8 below + randaug.hip; decoding stays on the host.
+// RandAugment is rscotr_img_frames_u8 below + randaug.hip; mmseg RandomRotate is the last pair (rscotr_img_aug_rot_u8 /
+// rscotr_seg_label_rot_u8); decoding stays on the host.
+// The flip word of every meta row is a bit set (mmcv imflip): bit 0 mirrors x ('horizontal'), bit 1 mirrors y ('vertical'),
+// 3 = both ('diagonal').
 //
 // HBM-bound: reads 3 B and writes 12 B per output pixel; one thread per output pixel x position, the three channel
 // planes written as coalesced float rows; source rows are read as bytes (3 consecutive bytes per thread: consecutive
@@ -18,7 +21,8 @@
 
 namespace rscotr {
 
-constexpr int IMGPREP_META = 10;  // int64 per sample: byte offset, H, W, row stride (bytes), x0, y0, crop w, crop h, flip, -
+// int64 per sample: byte offset, H, W, row stride (bytes), x0, y0, crop w, crop h, flip (bit 0: x, bit 1: y), -
+constexpr int IMGPREP_META = 10;
 
 struct PrepNorm {
   float mean[3], inv_std[3];
@@ -35,8 +39,8 @@ __global__ __launch_bounds__(256) void img_prep_kernel(const uint8_t* __restrict
   const int x0 = (int)m[4], y0 = (int)m[5], cw = (int)m[6], ch = (int)m[7], flip = (int)m[8];
   float v[3] = {0.f, 0.f, 0.f};  // mmcv Pad runs after Normalize with pad_val = 0
   if (y < ch && x < cw) {
-    const int sx = flip ? cw - 1 - x : x;
-    const uint8_t* p = src + off + (long)(y0 + y) * stride + (long)(x0 + sx) * 3;
+    const int sx = (flip & 1) ? cw - 1 - x : x, sy = (flip & 2) ? ch - 1 - y : y;
+    const uint8_t* p = src + off + (long)(y0 + sy) * stride + (long)(x0 + sx) * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float u = (float)p[to_rgb ? 2 - c : c];
@@ -61,8 +65,8 @@ __global__ __launch_bounds__(256) void seg_label_prep_kernel(const uint8_t* __re
   const int x0 = (int)m[4], y0 = (int)m[5], cw = (int)m[6], ch = (int)m[7], flip = (int)m[8];
   int64_t v = pad_val;
   if (y < ch && x < cw) {
-    const int sx = flip ? cw - 1 - x : x;
-    int l = src[off + (long)(y0 + y) * stride + (x0 + sx)];
+    const int sx = (flip & 1) ? cw - 1 - x : x, sy = (flip & 2) ? ch - 1 - y : y;
+    int l = src[off + (long)(y0 + sy) * stride + (x0 + sx)];
     if (reduce_zero_label) {  // mmseg LoadAnnotations: 0 -> 255, l -> l - 1, 254 -> 255
       l = (l == 0) ? 255 : l - 1;
       if (l == 254) l = 255;
@@ -123,7 +127,8 @@ extern "C" int rscotr_seg_label_prep_u8(const uint8_t* src, const int64_t* meta,
 // `src`, drawn on the host) and Normalize as in img_prep_kernel.  Reads <= n_y * n_x * 3 B and writes 12 B per output pixel.
 
 enum { RESAMPLE_NEAREST = 0, RESAMPLE_LINEAR = 1, RESAMPLE_PIL = 2 };
-// int64 per sample: byte offset, H, W, row stride (bytes), out w, out h, flip, x-table offset, y-table offset (int32 units),
+// int64 per sample: byte offset, H, W, row stride (bytes), out w, out h, flip (bit 0: the output x index is mirrored, bit 1:
+// the output y index), x-table offset, y-table offset (int32 units),
 // x taps K, y taps K, resample mode, photometric flags, hue delta, erase x0, y0, w, h, patch byte offset, -
 constexpr int IMGAUG_META = 20;
 // photometric flags (bit set = step applied; mmseg PhotoMetricDistortion draws randint(2) per step and the mode)
@@ -238,12 +243,12 @@ __device__ __forceinline__ void photometric(int u[3], int flags, int hue_delta, 
 // the host's per-axis tables.  Shared by img_aug_kernel and img_frames_kernel (the RandAugment path's first step).
 __device__ __forceinline__ void resample_u8(const uint8_t* __restrict__ src, const int64_t* __restrict__ m,
                                             const int32_t* __restrict__ tables, int x, int y, int u[3]) {
-  const int cw = (int)m[4];
+  const int cw = (int)m[4], ch = (int)m[5], flip = (int)m[6];
   const long off = m[0], stride = m[3];
-  const int j = m[6] ? cw - 1 - x : x;
+  const int j = (flip & 1) ? cw - 1 - x : x, i = (flip & 2) ? ch - 1 - y : y;
   const int kx = (int)m[9], ky = (int)m[10], mode = (int)m[11];
   const int32_t* tx = tables + m[7] + (long)j * (kx + 2);
-  const int32_t* ty = tables + m[8] + (long)y * (ky + 2);
+  const int32_t* ty = tables + m[8] + (long)i * (ky + 2);
   const uint8_t* base = src + off;
   if (mode == RESAMPLE_NEAREST) {
     const uint8_t* p = base + (long)ty[0] * stride + (long)tx[0] * 3;
@@ -315,8 +320,8 @@ __global__ __launch_bounds__(256) void seg_label_aug_kernel(const uint8_t* __res
   const int cw = (int)m[4], ch = (int)m[5];
   int64_t v = pad_val;
   if (y < ch && x < cw) {
-    const int j = m[6] ? cw - 1 - x : x;
-    const int sx = tables[m[7] + (long)j * (m[9] + 2)], sy = tables[m[8] + (long)y * (m[10] + 2)];
+    const int j = (m[6] & 1) ? cw - 1 - x : x, i = (m[6] & 2) ? ch - 1 - y : y;
+    const int sx = tables[m[7] + (long)j * (m[9] + 2)], sy = tables[m[8] + (long)i * (m[10] + 2)];
     int l = src[m[0] + (long)sy * m[3] + sx];
     if (reduce_zero_label) {  // mmseg LoadAnnotations: 0 -> 255, l -> l - 1, 254 -> 255
       l = (l == 0) ? 255 : l - 1;
@@ -352,7 +357,7 @@ __global__ __launch_bounds__(256) void img_frames_kernel(const uint8_t* __restri
 // the stage-1 entries, rounded and clamped to uint8 as the stored frame would be; the stage-2 blend is the same fixed-point
 // form.  So the result is bit-equal to the two passes, at <= 16 byte-triplet reads and 12 B written per output pixel.  The meta
 // row is rscotr_img_aug_u8's: words 0 .. 11 describe stage 1 (out w / h = the crop window of frame 1, flip 0: an early flip is
-// in the x entries), words 12 .. 15 = stage-2 x-table offset, y-table offset (entries of 4 words), final out w, out h.  A
+// in the x entries, and in the y entries when it is vertical or diagonal), words 12 .. 15 = stage-2 x-table offset, y-table offset (entries of 4 words), final out w, out h.  A
 // sample with one stage carries identity stage-2 entries (one tap of weight 2048).
 __global__ __launch_bounds__(256) void img_aug_chain_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
                                                             const int32_t* __restrict__ tables, float* __restrict__ out,
@@ -391,6 +396,144 @@ __global__ __launch_bounds__(256) void img_aug_chain_kernel(const uint8_t* __res
   o[0] = v[0];
   o[plane] = v[1];
   o[2 * plane] = v[2];
+}
+
+// ---- mmseg RandomRotate between the flipped window and the colour stages (rscotr_img_aug_rot_u8 / rscotr_seg_label_rot_u8) ---------
+// mmcv.imrotate = cv2.warpAffine(INTER_LINEAR, borderValue=pad_val) of the cropped, flipped uint8 window (cw, ch); the CPU path
+// stores that window and warps it, here it is never stored.  An output pixel takes its fixed-point source coordinate in WINDOW
+// space from the sample's warp table {adelta[cw], bdelta[cw], X0[ch], Y0[ch]} (rscotr_randaug_u8's layout: AB_SCALE 1024, the
+// float64 inverse matrix and round_delta folded in by the host): X = (X0[y] + adelta[x]) >> 5, sx = X >> 5, ax = X & 31, and the
+// same in y.  Each of the taps (sy .. sy + 1) x (sx .. sx + 1) that lies inside the window is the uint8 pixel img_aug_kernel
+// makes there (resample_u8: un-flipped and resampled from the raw source through the window's entries); a tap outside is the
+// pad colour (BGR).  The weights are (32 - ay | ay) * (32 - ax | ax) * 32: exact, they sum to 32768, no table; out =
+// (sum w * p + 2^14) >> 15.  A zero-weight tap is not read (ax = ay = 0: the pixel itself).  Then photometric, erasing,
+// normalize and pad as in img_aug_kernel.  rot: int32 rows of 4 {warp table offset (0 = the sample is not rotated and takes
+// img_aug_kernel's path: bit-equal to rscotr_img_aug_u8), pad B, pad G, pad R}.  Gathers are per lane and rely on L2 (a
+// wavefront's lanes walk consecutive output x, so its taps lie along one line of the window); <= 4 x the reads of img_aug_kernel.
+constexpr int IMGROT_ROW = 4;
+
+__global__ __launch_bounds__(256) void img_aug_rot_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
+                                                          const int32_t* __restrict__ tables,
+                                                          const float* __restrict__ params, const int32_t* __restrict__ rot,
+                                                          const int32_t* __restrict__ warp, float* __restrict__ out,
+                                                          int Hout, int Wout, PrepNorm nm, int to_rgb) {
+  const int b = blockIdx.z, y = blockIdx.y;
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= Wout) return;
+  const int64_t* m = meta + (long)b * IMGAUG_META;
+  const int32_t* r = rot + (long)b * IMGROT_ROW;
+  const int cw = (int)m[4], ch = (int)m[5];
+  float v[3] = {0.f, 0.f, 0.f};  // mmcv Pad runs after Normalize with pad_val = 0
+  if (y < ch && x < cw) {
+    int u[3];
+    if (r[0] == 0) {
+      resample_u8(src, m, tables, x, y, u);
+    } else {
+      const int32_t* wt = warp + r[0];
+      const int X = (wt[2 * cw + y] + wt[x]) >> 5, Y = (wt[2 * cw + ch + y] + wt[cw + x]) >> 5;
+      const int sx = X >> 5, sy = Y >> 5, ax = X & 31, ay = Y & 31;
+      int acc[3] = {0, 0, 0};
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const int w = (a ? ay : 32 - ay) * (t ? ax : 32 - ax) * 32;
+          if (w == 0) continue;
+          const int px = sx + t, py = sy + a;
+          int p[3] = {r[1], r[2], r[3]};
+          if (px >= 0 && px < cw && py >= 0 && py < ch) resample_u8(src, m, tables, px, py, p);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) acc[c] += w * p[c];
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) u[c] = (acc[c] + (1 << 14)) >> 15;  // (weights >= 0 that sum to 2^15: within [0, 255])
+    }
+    if (m[12]) photometric(u, (int)m[12], (int)m[13], params + (long)b * IMGAUG_PARAMS);
+    const int ex = x - (int)m[14], ey = y - (int)m[15];
+    if (ex >= 0 && ey >= 0 && ex < (int)m[16] && ey < (int)m[17]) {  // mmcls RandomErasing: patch overwrite
+      const uint8_t* p = src + m[18] + ((long)ey * m[16] + ex) * 3;
+      u[0] = p[0];
+      u[1] = p[1];
+      u[2] = p[2];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = ((float)u[to_rgb ? 2 - c : c] - nm.mean[c]) * nm.inv_std[c];
+  }
+  const long plane = (long)Hout * Wout;
+  float* o = out + (long)b * 3 * plane + (long)y * Wout + x;
+  o[0] = v[0];
+  o[plane] = v[1];
+  o[2 * plane] = v[2];
+}
+
+// The label companion: the same matrix, cv2 INTER_NEAREST (round_delta 512 folded in, sx = X >> 10).  Inside the window the raw
+// label is read through the nearest entries (un-flipped) and reduce_zero_label applies; outside it the value is the rot row's
+// seg_pad_val AS GIVEN (mmseg reduces at load time, before RandomRotate fills).  rot: int32 rows of 4 {warp table offset (0 =
+// not rotated: seg_label_aug_kernel's path), seg_pad_val, -, -}.  The canvas outside the window is pad_val (Pad's).
+__global__ __launch_bounds__(256) void seg_label_rot_kernel(const uint8_t* __restrict__ src,
+                                                            const int64_t* __restrict__ meta,
+                                                            const int32_t* __restrict__ tables,
+                                                            const int32_t* __restrict__ rot,
+                                                            const int32_t* __restrict__ warp, int64_t* __restrict__ out,
+                                                            int Hout, int Wout, int reduce_zero_label, int pad_val) {
+  const int b = blockIdx.z, y = blockIdx.y;
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= Wout) return;
+  const int64_t* m = meta + (long)b * IMGAUG_META;
+  const int32_t* r = rot + (long)b * IMGROT_ROW;
+  const int cw = (int)m[4], ch = (int)m[5];
+  int64_t v = pad_val;
+  if (y < ch && x < cw) {
+    int px = x, py = y;
+    if (r[0] != 0) {
+      const int32_t* wt = warp + r[0];
+      px = (wt[2 * cw + y] + wt[x]) >> 10;
+      py = (wt[2 * cw + ch + y] + wt[cw + x]) >> 10;
+    }
+    if (px >= 0 && px < cw && py >= 0 && py < ch) {
+      const int j = (m[6] & 1) ? cw - 1 - px : px, i = (m[6] & 2) ? ch - 1 - py : py;
+      const int sx = tables[m[7] + (long)j * (m[9] + 2)], sy = tables[m[8] + (long)i * (m[10] + 2)];
+      int l = src[m[0] + (long)sy * m[3] + sx];
+      if (reduce_zero_label) {  // mmseg LoadAnnotations: 0 -> 255, l -> l - 1, 254 -> 255
+        l = (l == 0) ? 255 : l - 1;
+        if (l == 254) l = 255;
+      }
+      v = l;
+    } else {
+      v = r[1];
+    }
+  }
+  out[((long)b * Hout + y) * Wout + x] = v;
+}
+
+extern "C" int rscotr_img_aug_rot_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, const float* params,
+                                     const int32_t* rot, const int32_t* warp, float* out, int B, int Hout, int Wout,
+                                     const float* mean3, const float* std3, int to_rgb, void* stream) {
+  if (int e = check_prep("rscotr_img_aug_rot_u8", src, meta, out, B, Hout, Wout)) return e;
+  if (B && Hout && Wout && (!tables || !params || !rot || !warp)) return fail(RSCOTR_E_ARG, "rscotr_img_aug_rot_u8: null pointer");
+  if (!mean3 || !std3) return fail(RSCOTR_E_ARG, "rscotr_img_aug_rot_u8: mean / std (3 host floats each) required");
+  PrepNorm nm;
+  for (int c = 0; c < 3; ++c) {
+    if (!(std3[c] > 0.f)) return fail(RSCOTR_E_ARG, "rscotr_img_aug_rot_u8: std[%d] must be positive", c);
+    nm.mean[c] = mean3[c];
+    nm.inv_std[c] = (float)(1.0 / (double)std3[c]);  // as rscotr_img_prep_u8
+  }
+  if (B == 0 || Hout == 0 || Wout == 0) return RSCOTR_OK;
+  img_aug_rot_kernel<<<dim3((Wout + 255) / 256, Hout, B), 256, 0, (hipStream_t)stream>>>(src, meta, tables, params, rot, warp,
+                                                                                       out, Hout, Wout, nm, to_rgb ? 1 : 0);
+  return check_launch("rscotr_img_aug_rot_u8");
+}
+
+extern "C" int rscotr_seg_label_rot_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, const int32_t* rot,
+                                       const int32_t* warp, int64_t* out, int B, int Hout, int Wout, int reduce_zero_label,
+                                       int pad_val, void* stream) {
+  if (int e = check_prep("rscotr_seg_label_rot_u8", src, meta, out, B, Hout, Wout)) return e;
+  if (B && Hout && Wout && (!tables || !rot || !warp)) return fail(RSCOTR_E_ARG, "rscotr_seg_label_rot_u8: null pointer");
+  if (B == 0 || Hout == 0 || Wout == 0) return RSCOTR_OK;
+  seg_label_rot_kernel<<<dim3((Wout + 255) / 256, Hout, B), 256, 0, (hipStream_t)stream>>>(src, meta, tables, rot, warp, out,
+                                                                                         Hout, Wout, reduce_zero_label, pad_val);
+  return check_launch("rscotr_seg_label_rot_u8");
 }
 
 extern "C" int rscotr_img_aug_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, const float* params,

@@ -3,15 +3,17 @@ step as HIP launches per batch, plus thin readers for the three datasets' on-dis
 
 Reference pipelines (configs/_base_/cls/resisc_swin_224.py:7-39, configs/_base_/det/dior.py:11-20,
 configs/_base_/seg/potsdam_IRRG_all.py:8-19):
-    decode (host) -> [Resize / RandomResizedCrop] -> RandomCrop window (seg) -> RandomFlip -> [PhotoMetricDistortion]
-           -> [RandomErasing] -> Normalize(mean, std, to_rgb) -> Pad -> ImageToTensor / DefaultFormatBundle -> collate
+    decode (host) -> [Resize / RandomResizedCrop] -> RandomCrop window (seg) -> RandomFlip -> [RandomRotate (seg)]
+           -> [PhotoMetricDistortion] -> [RandomErasing] -> Normalize(mean, std, to_rgb) -> Pad
+           -> ImageToTensor / DefaultFormatBundle -> collate
 (bracketed: the optional stages; mmcls RandAugment sits between RandomFlip and RandomErasing in the cls pipeline).
 Everything from the crop window on runs on the device; the host only draws the random decisions and uploads the raw bytes.
 
     resample   the integer resampling tables the host builds (cv2 bilinear, Pillow bicubic, nearest), cv2's bicubic remap weights
     randaug    RandAugment's configuration, draws, meta rows and warp tables
     autoaug    multi-scale Resize and mmdet AutoAugment (Resize / RandomCrop policies): draws, box chain, chain-launch tables
-    collate    DeviceCollate (one host plan under four launch routes), the dataset configs' settings, the seg TTA collate
+    rotate     mmseg RandomRotate: settings, draws, the rot rows and warp tables of the rotating launches
+    collate    DeviceCollate (one host plan under five launch routes), the dataset configs' settings, the seg TTA collate
     config     build_collate: an mm* pipeline config -> a collate
     datasets   FolderClsDataset, CocoDetDataset, TileSegDataset with their evaluate / pre_eval, DeviceLoader"""
 from .collate import (AUG_META, AUG_PARAMS, CLS_ERASING, IMG_NORM, PHOTOMETRIC, PM_BRIGHT, PM_CONTRAST, PM_CONTRAST_FIRST, PM_HUE,

@@ -10,7 +10,8 @@ two 11-bit weights) describe the final window from that crop.  RandomFlip stands
 the output index, which would be "resize, then flip" and differs in the rounded weights."""
 import numpy as np
 
-from .resample import _AXIS, RESAMPLE_LINEAR, RESAMPLE_NEAREST, _axis_linear, _table, mirror_x, rescale_size, scale_boxes
+from .resample import (_AXIS, FLIP_BITS, RESAMPLE_LINEAR, RESAMPLE_NEAREST, _axis_linear, _table, flip_boxes, mirror_x, rescale_size,
+                       scale_boxes)
 
 CROP_TYPES = ('relative_range', 'relative', 'absolute', 'absolute_range')  # mmdet RandomCrop
 
@@ -177,13 +178,15 @@ def aa_geometry(H, W, steps):
     return g
 
 
-def aa_boxes(boxes, labels, W, flip, steps):
-    """The box half of the same walk (mmdet 2.25, bbox_clip_border=True): RandomFlip.bbox_flip on the source width, Resize's
-    scale + clip, RandomCrop's shift + clip + `x2 > x1 and y2 > y1` filter (labels alike) -> (float32 (n, 4), int64 (n,))."""
+def aa_boxes(boxes, labels, W, flip, steps, H=None):
+    """The box half of the same walk (mmdet 2.25, bbox_clip_border=True): RandomFlip.bbox_flip on the source size, Resize's
+    scale + clip, RandomCrop's shift + clip + `x2 > x1 and y2 > y1` filter (labels alike) -> (float32 (n, 4), int64 (n,)).
+    `flip`: a direction ('horizontal' | 'vertical' | 'diagonal'; the last two need the source height `H`), None / False, or
+    True = 'horizontal'."""
     b = np.asarray(boxes, np.float32).reshape(-1, 4)
     l = np.asarray(labels, np.int64).reshape(-1)
     if flip:
-        b = np.stack([np.float32(W) - b[:, 2], b[:, 1], np.float32(W) - b[:, 0], b[:, 3]], -1)
+        b = flip_boxes(b, 'horizontal' if flip is True else flip, W, H)
     for s in steps:
         if s[0] == 'resize':
             b = scale_boxes(b, step_scale_factor(s), (s[2][1], s[2][0]))
@@ -222,8 +225,11 @@ def chain_tables(tabs, d, img_shape, Hout, Wout):
     assert 0 <= fx and 0 <= fy and fx + fw <= r2w and fy + fh <= r2h and fw <= Wout and fh <= Hout
     mode = RESAMPLE_NEAREST if (sw, sh) == (rw, rh) else RESAMPLE_LINEAR
     tx, ty = _AXIS[mode](sw, rw, sx, x0, cw), _AXIS[mode](sh, rh, sy, y0, ch)
-    if d['flip']:
+    bits = FLIP_BITS[d.get('flip_direction', 'horizontal') if d['flip'] else None]
+    if bits & 1:
         tx = mirror_x(tx, W)
+    if bits & 2:
+        ty = mirror_x(ty, H)
     t2x, t2y = _stage2_axis(cw, r2w, fx, fw), _stage2_axis(ch, r2h, fy, fh)
     for t, dim in ((tx, W), (ty, H), (t2x, cw), (t2y, ch)):
         assert (t[:, 0] >= 0).all() and (t[:, 1] >= 1).all() and (t[:, 0] + t[:, 1] <= dim).all()

@@ -9,7 +9,12 @@ a seeded run makes the same decisions, and sends the raw bytes with the launches
              over the per-axis tables of resample.py;
   RandAugment `rand_augment=` (cls): `rscotr_img_frames_u8` -> `rscotr_randaug_u8` per slot -> `rscotr_img_aug_u8` (randaug.py);
   chain      `auto_augment=` (det), when a sample of the batch drew a policy with two Resizes: `rscotr_img_aug_chain_u8`, both
-             resamplings in one launch (autoaug.py); a batch of one-Resize samples is the table route's."""
+             resamplings in one launch (autoaug.py); a batch of one-Resize samples is the table route's;
+  rotate     `rotate=` (seg), when a sample of the batch drew a rotation: the table route's upload with the warp tables of
+             rotate.py behind it, `rscotr_img_aug_rot_u8` (+ `rscotr_seg_label_rot_u8`), every sample in the one launch; a
+             batch that drew none is the table route's.
+RandomFlip's direction ('horizontal' | 'vertical' | 'diagonal') is the flip word of the meta rows on every route; in front of
+the geometry (`auto_augment=`) it is mirrored into the x / y entries."""
 import ctypes
 import math
 import random
@@ -22,8 +27,9 @@ from .. import ops
 from .._lib import lib
 from .autoaug import aa_boxes, aa_config, aa_draw, aa_geometry, chain_tables, check_resize, resize_shape
 from .randaug import RA_STATS, _ra_config, ra_draws, ra_slot_rows
-from .resample import (RESAMPLE_LINEAR, RESAMPLE_NEAREST, RESAMPLE_PIL, _axis_nearest, _AxisTables, _round_up, cubic_weight_table,
-                       scale_boxes)
+from .resample import (FLIP_BITS, RESAMPLE_LINEAR, RESAMPLE_NEAREST, RESAMPLE_PIL, _axis_nearest, _AxisTables, _round_up,
+                       cubic_weight_table, flip_boxes, scale_boxes)
+from .rotate import rotate_config, rotate_draw, rotate_rows
 
 IMG_NORM = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
 META = 10  # include/rscotr.h: rscotr_img_prep_u8's meta row
@@ -40,11 +46,45 @@ def _host_floats(v):
     return arr, ctypes.cast(arr, ctypes.c_void_p)
 
 
+def _flip_bits(d):
+    """The flip word of a meta row (include/rscotr.h) for the draw `d`; a draw without a direction flips horizontally."""
+    return FLIP_BITS[d.get('flip_direction', 'horizontal')] if d['flip'] else 0
+
+
+def _flip_config(task, direction, prob):
+    """RandomFlip's `direction` and probability, validated -> (direction | list of directions, prob | list of probs)."""
+    known = ('horizontal', 'vertical', 'diagonal') if task == 'det' else ('horizontal', 'vertical')
+    if isinstance(direction, (list, tuple)):
+        if task != 'det':
+            raise ValueError(f"flip_direction: task {task!r} takes one direction (mmseg / mmcls), not {direction!r}")
+        direction = list(direction)
+        if not direction or len(set(direction)) != len(direction):
+            raise ValueError(f'flip_direction: {direction!r} must be a non-empty list of different directions')
+        for dr in direction:
+            if dr not in known:
+                raise ValueError(f'flip_direction: unknown direction {dr!r} (one of {known})')
+        if isinstance(prob, (list, tuple)):
+            prob = [float(v) for v in prob]
+            if len(prob) != len(direction):
+                raise ValueError(f'flip_prob: {len(prob)} ratios for {len(direction)} directions')
+        else:
+            prob = float(prob or 0.0)
+        ratios = prob if isinstance(prob, list) else [prob]
+        if min(ratios) < 0 or sum(ratios) > 1:
+            raise ValueError(f'flip_prob: {prob!r} must be non-negative and sum to at most 1')
+        return direction, prob
+    if direction not in known:
+        raise ValueError(f'flip_direction: unknown direction {direction!r} for task {task!r} (one of {known})')
+    if isinstance(prob, (list, tuple)):
+        raise ValueError('flip_prob: a list of ratios needs a list of directions')
+    return direction, prob
+
+
 def _aug_row(off, shape, stride, d, geo, pm=None, erase=None, patch_off=0):
     """One rscotr_img_aug_u8 meta row (include/rscotr.h): a source of `shape` at byte offset `off`, the window and flip of the
     draw `d`, the tables `geo` (`_AxisTables.add_window`), the photometric draws and the erasing draws with their patch's offset."""
     (_, _, cw, ch), (mode, xt, kx, yt, ky) = d['win'], geo
-    flip = int(d['flip'] and not d.get('flip_first', False))  # (a flip in front of the geometry is in the x entries)
+    flip = 0 if d.get('flip_first', False) else _flip_bits(d)  # (a flip in front of the geometry is in the x / y entries)
     row = [off, shape[0], shape[1], stride, cw, ch, flip, xt, yt, kx, ky, mode] + [0] * (AUG_META - 12)
     if pm is not None:
         row[12], row[13] = pm[0], pm[4]
@@ -64,8 +104,11 @@ class DeviceCollate:
     def __init__(self, task, device, img_norm_cfg=None, flip_prob=0.5, size_divisor=None, crop_size=None,
                  cat_max_ratio=1.0, reduce_zero_label=False, seg_pad_val=255, ignore_index=255, resize=None,
                  random_resized_crop=None, photometric=None, random_erasing=None, resize_backend='cv2',
-                 rand_augment=None, labels=True, auto_augment=None):
-        """Optional stages (None = off; any of them on routes the batch through `rscotr_img_aug_u8`):
+                 rand_augment=None, labels=True, auto_augment=None, flip_direction='horizontal', rotate=None):
+        """flip_direction: RandomFlip's direction, 'horizontal' | 'vertical' (mmseg, mmcls, mmdet) or, for task 'det', 'diagonal'
+                or a list of directions; with a list mmdet draws one of them or none per sample, `flip_prob` a float shared
+                equally among them or a list of ratios, one per direction, that sum to at most 1.
+        Optional stages (None = off; any of them on routes the batch through `rscotr_img_aug_u8`):
         resize: mmseg / mmdet Resize, dict(img_scale=(long, short), ratio_range=None | (lo, hi), keep_ratio=True), or with
                 img_scale=[(long, short), ...] and multiscale_mode='value' | 'range' (a scale drawn per sample), or
                 mmcls Resize, dict(size=(h, w)) (a fixed size);
@@ -79,9 +122,13 @@ class DeviceCollate:
         labels: False = a seg batch without `gt_semantic_seg` (test time: the label maps are neither staged nor resampled);
         auto_augment: mmdet AutoAugment (task 'det' only), dict(policies=[[Resize | RandomCrop dicts]]) (autoaug.py): RandomFlip
                 is drawn and applied FIRST, then one policy per sample; a sample whose policy resizes twice sends the batch
-                through `rscotr_img_aug_chain_u8`.  It is the whole geometry: no other optional stage goes with it."""
+                through `rscotr_img_aug_chain_u8`.  It is the whole geometry: no other optional stage goes with it;
+        rotate: mmseg RandomRotate (task 'seg' only), dict(prob, degree, pad_val=0, seg_pad_val=255, center=None) (rotate.py):
+                applied to the cropped, flipped window, in front of `photometric`; a batch in which a sample drew a rotation
+                goes through `rscotr_img_aug_rot_u8` (+ `rscotr_seg_label_rot_u8`)."""
         assert task in ('cls', 'det', 'seg')
         self.task, self.device = task, torch.device(device)
+        self.flip_direction, flip_prob = _flip_config(task, flip_direction, flip_prob)
         cfg = dict(IMG_NORM if img_norm_cfg is None else img_norm_cfg)
         self.mean, self.std, self.to_rgb = cfg['mean'], cfg['std'], bool(cfg.get('to_rgb', True))
         self.flip_prob, self.size_divisor, self.crop_size = flip_prob, size_divisor, crop_size
@@ -116,8 +163,11 @@ class DeviceCollate:
             if resize_backend != 'cv2':
                 raise NotImplementedError(f'AutoAugment with resize_backend={resize_backend!r}: a chain resamples cv2 bilinear')
             self.auto_augment = aa_config(auto_augment)
+        if rotate is not None and task != 'seg':
+            raise ValueError("rotate is for task 'seg' only: mmseg RandomRotate turns the image and its label map, not boxes")
+        self.rotate = None if rotate is None else rotate_config(rotate)
         self.augmented = any(x is not None for x in (self.resize, self.rrc, self.photometric, self.erasing,
-                                                     self.rand_augment, self.auto_augment))
+                                                     self.rand_augment, self.auto_augment, self.rotate))
         self.skipped = []  # transforms build_collate was told to skip
         self.labels = bool(labels)
         self._stage = None  # pinned byte staging buffer (grow-only)
@@ -224,19 +274,31 @@ class DeviceCollate:
             patch = np.clip(patch.astype(np.int32), 0, 255).astype(np.uint8)
         return left, top, w, h, patch
 
+    def _flip_draw(self, rng):
+        """RandomFlip's draw -> the direction applied, or None.  One direction: rand() < flip_prob.  A list (mmdet):
+        np.random.choice(directions + [None], p=ratios + [1 - sum(ratios)]), drawn by index (one uniform, as rand())."""
+        if not isinstance(self.flip_direction, list):
+            return self.flip_direction if rng.rand() < self.flip_prob else None
+        n = len(self.flip_direction)
+        ratios = list(self.flip_prob) if isinstance(self.flip_prob, list) else [self.flip_prob / n] * n
+        k = int(rng.choice(n + 1, p=ratios + [1 - sum(ratios)]))
+        return self.flip_direction[k] if k < n else None
+
     def draw(self, img_shape, seg, rng, py_rng=None):
-        """Every random decision of one sample, in the reference's order (geometry, crop, flip, photometric, RandAugment,
-        erasing): a dict with the source rectangle `src` (x, y, w, h), the resized frame `rsz` (w, h), the window `win`
-        (x0, y0, w, h) in that frame, `flip`, `pm` (photometric draws or None), `ra` (the RandAugment plan, `ra_draws`; absent
-        when the stage is off) and `erase` (or None).  `py_rng`: the Python-side generator of RandAugment (default `random`).
+        """Every random decision of one sample, in the reference's order (geometry, crop, flip, rotate, photometric,
+        RandAugment, erasing): a dict with the source rectangle `src` (x, y, w, h), the resized frame `rsz` (w, h), the window
+        `win` (x0, y0, w, h) in that frame, `flip` and `flip_direction` (the direction applied, or None), `rotate` (the degree
+        applied or None; absent when the stage is off), `pm` (photometric draws or None), `ra` (the RandAugment plan, `ra_draws`;
+        absent when the stage is off) and `erase` (or None).  `py_rng`: the Python-side generator of RandAugment (default `random`).
         With every optional stage off these are the window and flip draws of the plain route.  With `auto_augment` the flip is
         drawn first and applies to the source (`flip_first`), `steps` is the drawn policy's walk (`aa_draw`) and `chain` is None or
         the second stage, dict(win1: the crop window of frame `rsz`, rsz2: the frame `win` lies in) (`aa_geometry`)."""
         H, W = img_shape[:2]
         if self.auto_augment is not None:  # mmdet RandomFlip, then AutoAugment: one policy's Resize / RandomCrop draws
-            flip = bool(rng.rand() < self.flip_prob)
+            direction = self._flip_draw(rng)
             policy, steps = aa_draw(self.auto_augment, H, W, rng)
-            return dict(aa_geometry(H, W, steps), flip=flip, flip_first=True, policy=policy, steps=steps, pm=None, erase=None)
+            return dict(aa_geometry(H, W, steps), flip=direction is not None, flip_direction=direction, flip_first=True,
+                        policy=policy, steps=steps, pm=None, erase=None)
         if self.rrc is not None:
             oy, ox, th, tw = self._rrc_params(H, W, rng)
             size = self.rrc['size']
@@ -259,7 +321,10 @@ class DeviceCollate:
             win = self._crop_window_hw(rsz[1], rsz[0], lab, rng)
         else:
             win = (0, 0, rsz[0], rsz[1])
-        d = dict(src=src, rsz=rsz, win=win, flip=bool(rng.rand() < self.flip_prob), pm=None, erase=None)
+        direction = self._flip_draw(rng)
+        d = dict(src=src, rsz=rsz, win=win, flip=direction is not None, flip_direction=direction, pm=None, erase=None)
+        if self.rotate is not None:
+            d['rotate'] = rotate_draw(self.rotate, rng)
         if self.photometric is not None:
             d['pm'] = self._photometric_draws(rng)
         if self.rand_augment is not None:
@@ -291,8 +356,10 @@ class DeviceCollate:
         for im, d in zip(imgs, ds):
             (_, _, sw, sh), (rw, rh), (_, _, cw, ch) = d['src'], d['rsz'], d['win']
             m = dict(ori_shape=im.shape, img_shape=(ch, cw, 3), pad_shape=(Hout, Wout, 3), flip=d['flip'],
-                     flip_direction='horizontal' if d['flip'] else None, scale_factor=1.0,
+                     flip_direction=d['flip_direction'], scale_factor=1.0,
                      img_norm_cfg=dict(mean=self.mean, std=self.std, to_rgb=self.to_rgb))
+            if self.rotate is not None:
+                m['rotate_degree'] = d['rotate']  # the degree that was applied, or None
             if resized:
                 m['scale_factor'] = np.array([rw / sw, rh / sh, rw / sw, rh / sh], dtype=np.float32)
                 m['keep_ratio'] = bool(self.resize is not None and self.resize.get('keep_ratio') and 'size' not in self.resize)
@@ -322,13 +389,12 @@ class DeviceCollate:
                 hb = np.asarray(s['gt_bboxes'], dtype=np.float32).reshape(-1, 4)
                 hl = np.asarray(s['gt_labels'], dtype=np.int64).reshape(-1)
                 if self.auto_augment is not None:  # flip, then the policy's scale / shift / clip / drop chain
-                    hb, hl = aa_boxes(hb, hl, s['img'].shape[1], d['flip'], d['steps'])
+                    hb, hl = aa_boxes(hb, hl, s['img'].shape[1], d['flip_direction'], d['steps'], H=s['img'].shape[0])
                 if p.resized:
                     hb = scale_boxes(hb, m['scale_factor'], m['img_shape'])
-                cw = d['win'][2]
                 if d['flip'] and self.auto_augment is None:
-                    # mmdet RandomFlip.bbox_flip, horizontal (on the host: the boxes are a few dozen floats)
-                    hb = np.stack([np.float32(cw) - hb[:, 2], hb[:, 1], np.float32(cw) - hb[:, 0], hb[:, 3]], -1)
+                    # mmdet RandomFlip.bbox_flip on the window (on the host: the boxes are a few dozen floats)
+                    hb = flip_boxes(hb, d['flip_direction'], d['win'][2], d['win'][3])
                 boxes.append(torch.from_numpy(np.ascontiguousarray(hb)).to(self.device))
                 labels.append(torch.from_numpy(np.ascontiguousarray(hl)).to(self.device))
                 hboxes.append(np.ascontiguousarray(hb))
@@ -392,9 +458,9 @@ class DeviceCollate:
         arrays = p.imgs + p.segs + [meta, lmeta]
         offs = self._upload_offsets(arrays)
         for b, (src, d) in enumerate(zip(p.imgs, p.ds)):
-            meta[b] = [offs[b], src.shape[0], src.shape[1], src.shape[1] * 3, *d['win'], int(d['flip']), 0]
+            meta[b] = [offs[b], src.shape[0], src.shape[1], src.shape[1] * 3, *d['win'], _flip_bits(d), 0]
         for b, (src, d) in enumerate(zip(p.segs, p.ds)):
-            lmeta[b] = [offs[B + b], src.shape[0], src.shape[1], src.shape[1], *d['win'], int(d['flip']), 0]
+            lmeta[b] = [offs[B + b], src.shape[0], src.shape[1], src.shape[1], *d['win'], _flip_bits(d), 0]
         buf, offs = self._upload(arrays)
         ptr = buf.data_ptr()
         self._launch_img('rscotr_img_prep_u8', (ptr, ptr + offs[-2]), p)
@@ -402,18 +468,24 @@ class DeviceCollate:
 
     def _launch_tables(self, p):
         """The same with a resized frame and the colour stages in front.  Layout of the one upload: images | label maps |
-        erasing patches | tables | params | meta | label meta."""
+        erasing patches | tables | params | meta | label meta; on the rotate route (a sample of the batch drew a rotation)
+        then | rot rows | label rot rows | warp tables, and the launches are the rotating pair."""
         B = len(p.imgs)
         tabs = _AxisTables()
-        geo = [tabs.add_window(self.resample, d, p.Hout, p.Wout,
-                               mirror_w=a.shape[1] if d['flip'] and d.get('flip_first', False) else None)
-               for a, d in zip(p.imgs, p.ds)]
+        first = [_flip_bits(d) if d.get('flip_first', False) else 0 for d in p.ds]  # (a flip in front of the geometry)
+        geo = [tabs.add_window(self.resample, d, p.Hout, p.Wout, mirror_w=a.shape[1] if f & 1 else None,
+                               mirror_h=a.shape[0] if f & 2 else None)
+               for a, d, f in zip(p.imgs, p.ds, first)]
         lgeo = [tabs.add_window(RESAMPLE_NEAREST, d, p.Hout, p.Wout) for _, d in zip(p.segs, p.ds)]
         tabs.check([a.shape for a in p.imgs])  # (the label tables are the nearest form of the same geometry on the same shapes)
         patches = [d['erase'][4] for d in p.ds if d['erase'] is not None]
         params = np.zeros((max(B, 1), AUG_PARAMS), np.float32)
         meta, lmeta = np.zeros((max(B, 1), AUG_META), np.int64), np.zeros((max(B, 1), AUG_META), np.int64)
         arrays = p.imgs + p.segs + patches + [tabs.flat(), params, meta, lmeta]
+        rotated = self.rotate is not None and any(d['rotate'] is not None for d in p.ds)
+        if rotated:
+            rot, lrot, warp = rotate_rows(self.rotate, p.ds, labels=bool(p.segs))
+            arrays += [rot, lrot, warp]
         offs = self._upload_offsets(arrays)
         patch_offs = iter(offs[B + len(p.segs):])
         for b, (src, d, g) in enumerate(zip(p.imgs, p.ds, geo)):
@@ -425,9 +497,15 @@ class DeviceCollate:
             lmeta[b] = _aug_row(offs[B + b], src.shape, src.shape[1], d, g)
         buf, offs = self._upload(arrays)
         ptr = buf.data_ptr()
-        p_tab, p_prm, p_meta, p_lmeta = [ptr + o for o in offs[-4:]]
-        self._launch_img('rscotr_img_aug_u8', (ptr, p_meta, p_tab, p_prm), p)
-        self._launch_labels('rscotr_seg_label_aug_u8', (ptr, p_lmeta, p_tab), p)
+        n = len(p.imgs) + len(p.segs) + len(patches)
+        p_tab, p_prm, p_meta, p_lmeta = [ptr + o for o in offs[n:n + 4]]
+        if rotated:
+            p_rot, p_lrot, p_warp = [ptr + o for o in offs[n + 4:]]
+            self._launch_img('rscotr_img_aug_rot_u8', (ptr, p_meta, p_tab, p_prm, p_rot, p_warp), p)
+            self._launch_labels('rscotr_seg_label_rot_u8', (ptr, p_lmeta, p_tab, p_lrot, p_warp), p)
+        else:
+            self._launch_img('rscotr_img_aug_u8', (ptr, p_meta, p_tab, p_prm), p)
+            self._launch_labels('rscotr_seg_label_aug_u8', (ptr, p_lmeta, p_tab), p)
 
     def _launch_chain(self, p):
         """The det batch of AutoAugment in which a sample resizes twice: `rscotr_img_aug_chain_u8`, every sample in the one
@@ -595,7 +673,7 @@ class SegTTACollate:
         if self.tta.get('flip', False):
             for d in (dirs if isinstance(dirs, (list, tuple)) else [dirs]):
                 if d != 'horizontal':
-                    raise NotImplementedError(f"MultiScaleFlipAug(flip_direction={d!r}): the input kernels flip horizontally only")
+                    raise NotImplementedError(f"MultiScaleFlipAug(flip_direction={d!r}): the test-time views flip horizontally only")
         self.views = None if self.tta.get('img_scale') is None else self._plan(None)
         self._collates = {}
 

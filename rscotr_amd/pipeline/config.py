@@ -4,6 +4,11 @@ from .collate import PHOTOMETRIC, DeviceCollate, SegTTACollate
 from .randaug import ra_unsupported
 
 _PASSIVE = {'LoadImageFromFile', 'ImageToTensor', 'ToTensor', 'DefaultFormatBundle', 'Collect', 'Normalize'}
+# RandomRotate's place: the collate rotates the cropped, flipped window, in front of the colour stages
+_BEFORE_ROTATE = ('Resize', 'RandomCrop', 'RandomFlip', 'RandomResizedCrop', 'RandomRotate')
+_AFTER_ROTATE = ('PhotoMetricDistortion', 'Normalize', 'Pad')
+_ROTATE_PLACE = ('the device collate rotates the cropped, flipped window, after Resize / RandomCrop / RandomFlip and before '
+                 'PhotoMetricDistortion / Normalize / Pad')
 
 
 def build_collate(task, pipeline_cfg, device, unsupported='raise'):
@@ -12,7 +17,11 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
     Understood: LoadImageFromFile, LoadAnnotations (reduce_zero_label), Resize (mmseg / mmdet img_scale + ratio_range +
     keep_ratio, for 'det' and 'seg' also a list of scales + multiscale_mode 'value' | 'range'; mmcls size + backend +
     interpolation), AutoAugment for task 'det' (policies of Resize and mmdet RandomCrop(crop_type, allow_negative_crop=True)
-    behind a RandomFlip: the DETR multi-scale recipe), RandomResizedCrop, RandomCrop, RandomFlip, PhotoMetricDistortion,
+    behind a RandomFlip: the DETR multi-scale recipe), RandomResizedCrop, RandomCrop, RandomFlip (direction 'horizontal' |
+    'vertical', for 'det' also 'diagonal' or a list of directions with mmdet's flip_ratio, a float or a list; an unknown
+    direction, or a list for 'cls' / 'seg', raises ValueError), RandomRotate for task 'seg' (prob, degree, pad_val, seg_pad_val,
+    center; it stands after Resize / RandomCrop / RandomFlip and before PhotoMetricDistortion / Normalize / Pad: anywhere else,
+    or with auto_bound=True, it raises NotImplementedError, for another task ValueError), PhotoMetricDistortion,
     RandomErasing, Normalize, Pad, ImageToTensor, ToTensor, DefaultFormatBundle, Collect, MultiScaleFlipAug (its single
     scale and its transforms; flip=False — for task 'seg' also flip=True, `img_ratios` and several scales, up to
     SEG_TTA_MAX_VIEWS views: the result is then a SegTTACollate) and RandAugment when `policies` is a non-empty list of the 13 implemented types
@@ -21,12 +30,15 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
     listed in `collate.skipped`, and the random stream no longer matches the reference's (the skipped transform's draws are
     not made)."""
     assert unsupported in ('raise', 'skip')
-    kw, skipped, norm, tta = dict(flip_prob=0.0), [], None, None
+    kw, skipped, norm, tta, seen = dict(flip_prob=0.0), [], None, None, []
 
     def visit(t, scale=None):
         nonlocal norm, tta
         t = dict(t)
         typ = t.pop('type')
+        if 'RandomRotate' in seen and typ in _BEFORE_ROTATE:
+            raise NotImplementedError(f'{typ} after RandomRotate: {_ROTATE_PLACE}')
+        seen.append(typ)
         if typ in _PASSIVE:
             if typ == 'Normalize':
                 norm = t
@@ -104,6 +116,16 @@ def build_collate(task, pipeline_cfg, device, unsupported='raise'):
             raise NotImplementedError('RandomFlip after AutoAugment (the chain flips the source in front of its geometry)')
         elif typ == 'RandomFlip':
             kw['flip_prob'] = t.get('flip_prob', t.get('flip_ratio', t.get('prob', 0.0))) or 0.0
+            kw['flip_direction'] = t.get('direction', 'horizontal')  # (DeviceCollate validates it for the task)
+        elif typ == 'RandomRotate':
+            if task != 'seg':
+                raise ValueError(f"RandomRotate is mmseg's: task 'seg' only, not {task!r}")
+            if t.get('auto_bound', False):
+                raise NotImplementedError('RandomRotate(auto_bound=True) changes the frame size')
+            late = [s for s in seen[:-1] if s in _AFTER_ROTATE]
+            if late:
+                raise NotImplementedError(f'RandomRotate after {late[0]}: {_ROTATE_PLACE}')
+            kw['rotate'] = t
         elif typ == 'PhotoMetricDistortion':
             kw['photometric'] = dict(PHOTOMETRIC, **t)
         elif typ == 'RandomErasing':

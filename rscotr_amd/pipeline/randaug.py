@@ -98,8 +98,14 @@ def _ra_matrix(p, m, w, h):
 
 
 def _ra_warp_table(M, w, h, bicubic):
+    """`warp_table` of a RandAugment warp: bicubic or nearest."""
+    return warp_table(M, w, h, 16 if bicubic else 512)
+
+
+def warp_table(M, w, h, rd):
     """cv2.warpAffine without WARP_INVERSE_MAP: M inverted in float64 as OpenCV does, then the int32 coordinate tables
-    adelta[w] | bdelta[w] | X0[h] | Y0[h] (AB_SCALE = 1024, round_delta = 16 bicubic / 512 nearest folded into X0, Y0)."""
+    adelta[w] | bdelta[w] | X0[h] | Y0[h] (AB_SCALE = 1024, round_delta `rd` = 16 bicubic and bilinear / 512 nearest folded into
+    X0, Y0)."""
     m0, m1, m2, m3, m4, m5 = [float(v) for v in M]
     D = m0 * m4 - m1 * m3
     D = 1.0 / D if D != 0 else 0.0
@@ -108,7 +114,6 @@ def _ra_warp_table(M, w, h, bicubic):
     b1 = -m0 * m2 - m1 * m5
     b2 = -m3 * m2 - m4 * m5
     x, y = np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64)
-    rd = 16 if bicubic else 512
     t = np.concatenate([np.rint(m0 * x * 1024), np.rint(m3 * x * 1024), np.rint((m1 * y + b1) * 1024) + rd,
                         np.rint((m4 * y + b2) * 1024) + rd])
     return np.clip(t, -2 ** 30, 2 ** 30).astype(np.int32)  # (a coordinate that large is outside any frame either way)

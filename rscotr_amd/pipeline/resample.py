@@ -78,7 +78,8 @@ def _axis_pil_bicubic(n_in, n_out, src0, o0, count):
 
 def mirror_x(t, W):
     """The x entries of a row of width W that is flipped left-right BEFORE it is resampled: taps first .. first + n - 1 of the
-    flipped row are taps W - first - n .. W - first - 1 of the stored one, with the weights in reverse order (<= 2 taps)."""
+    flipped row are taps W - first - n .. W - first - 1 of the stored one, with the weights in reverse order (<= 2 taps).  The
+    y entries of a column of height W that is flipped upside down are the same thing."""
     assert t.shape[1] <= 4
     t = t.copy()
     t[:, 0] = W - t[:, 0] - t[:, 1]
@@ -103,10 +104,10 @@ class _AxisTables:
         self.size += t.size
         return self.size - t.size, t.shape[1] - 2
 
-    def add_window(self, mode, d, Hout, Wout, mirror_w=None):
+    def add_window(self, mode, d, Hout, Wout, mirror_w=None, mirror_h=None):
         """The x and y tables of one sample's draw `d` (DeviceCollate.draw): identity nearest entries where it is not resized
         (its window is read as is) -> (mode, x offset, x taps, y offset, y taps).  `mirror_w`: the source, that many pixels
-        wide, is flipped left-right in front of the resampling (`mirror_x`)."""
+        wide, is flipped left-right in front of the resampling (`mirror_x`); `mirror_h`: that many pixels high, upside down."""
         (sx, sy, sw, sh), (rw, rh), (x0, y0, cw, ch) = d['src'], d['rsz'], d['win']
         assert 0 <= x0 and 0 <= y0 and x0 + cw <= rw and y0 + ch <= rh and cw <= Wout and ch <= Hout
         mode = RESAMPLE_NEAREST if (sw, sh) == (rw, rh) else mode
@@ -114,7 +115,10 @@ class _AxisTables:
         if mirror_w is not None:
             tx = mirror_x(tx, mirror_w)
         xt, kx = self.add(tx)
-        yt, ky = self.add(_AXIS[mode](sh, rh, sy, y0, ch))
+        ty = _AXIS[mode](sh, rh, sy, y0, ch)
+        if mirror_h is not None:
+            ty = mirror_x(ty, mirror_h)
+        yt, ky = self.add(ty)
         return mode, xt, kx, yt, ky
 
     def check(self, shapes):
@@ -146,6 +150,23 @@ def scale_boxes(bboxes, scale_factor, img_shape):
     b[:, 0::2] = np.clip(b[:, 0::2], 0, img_shape[1])
     b[:, 1::2] = np.clip(b[:, 1::2], 0, img_shape[0])
     return b
+
+
+# mmcv imflip's directions as the flip word of the kernels' meta rows (include/rscotr.h): bit 0 mirrors x, bit 1 mirrors y
+FLIP_BITS = {None: 0, 'horizontal': 1, 'vertical': 2, 'diagonal': 3}
+
+
+def flip_boxes(bboxes, direction, w, h):
+    """mmdet RandomFlip.bbox_flip on an (h, w) image: 'horizontal' x1' = w - x2, x2' = w - x1; 'vertical' the same in y with h;
+    'diagonal' both; None: unchanged.  float32 (n, 4)."""
+    b = np.asarray(bboxes, np.float32).reshape(-1, 4)
+    x1, y1, x2, y2 = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+    bits = FLIP_BITS[direction]
+    if bits & 1:
+        x1, x2 = np.float32(w) - x2, np.float32(w) - x1
+    if bits & 2:
+        y1, y2 = np.float32(h) - y2, np.float32(h) - y1
+    return np.stack([x1, y1, x2, y2], -1)
 
 
 _CUBIC_WTAB = None
