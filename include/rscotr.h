@@ -32,8 +32,8 @@ extern "C" {
  * round 6 = 7; 11 added the resampling input entries rscotr_img_aug_u8 / rscotr_seg_label_aug_u8; the
  * evaluation entries since — seg_predict / seg_areas, det_decode / det_match, seg_predict_tta, seg_predict_slide — are additive and change no
  * argument list, so they keep 11: a library without them fails to bind by name; the seg head's scheme-1 entries rscotr_seg_mix_* and
- * the det input chain rscotr_img_aug_chain_u8 likewise, and the Dice, Tversky and focal seg losses
- * rscotr_upsample_dice_* / rscotr_upsample_tversky_* / rscotr_upsample_focal_*, and the rotation input entries
+ * the det input chain rscotr_img_aug_chain_u8 likewise, and the Dice, Tversky, focal and Lovasz seg losses
+ * rscotr_upsample_dice_* / rscotr_upsample_tversky_* / rscotr_upsample_focal_* / rscotr_upsample_lovasz_*, and the rotation input entries
  * rscotr_img_aug_rot_u8 / rscotr_seg_label_rot_u8).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
  * its first call (rscotr_amd/_lib.py does) — a stale .so would take a stream handle for a pointer. */
 #define RSCOTR_ABI_VERSION 11
@@ -608,6 +608,44 @@ int rscotr_upsample_focal_fwd(const float* logit, const int64_t* label, const fl
 int rscotr_upsample_focal_bwd(const float* logit, const int64_t* label, const float* alpha_per_class, const float* class_weight,
                               const float* grad_scale, float* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index,
                               float gamma, float alpha, void* stream);
+
+/* ---- fused bilinear upsample + softmax + Lovasz-softmax on a segmented device sort (seg loss; additive entries: the ABI revision
+ * is unchanged) ---------------------------------------------------------------------------------------------------------------
+ * mmseg 0.28 LovaszLoss, loss_type='multi_class', as BaseDecodeHead.losses reaches it, without the up-sampled logits or the
+ * probabilities in memory:
+ *   p = softmax(resize(logit, (H,W), bilinear, align_corners=False), dim=1).  A SEGMENT is one class slot (class c = slots[s], or
+ *   s itself when slots is NULL) over the pixels with label != ignore_index of the whole batch (per_image = 0) or of one image
+ *   (per_image = 1).  fg = [label == c] (a label outside [0, C) is background for every class), e = |fg - p_c|, sorted descending
+ *   with equal errors in ascending flat pixel order (b, y, x); G = sum fg, F_k the foreground count of the first k + 1 sorted
+ *   elements, I_k = G - F_k, U_k = G + (k + 1 - F_k), g_k = 1 / U_k at a foreground element, I_k / (U_k (U_k - 1)) at a background
+ *   one (G == 0: g_0 = 1, all others 0), loss_seg = sum_k e_(k) g_k.  A segment is summed when it has a valid pixel and
+ *   (present == 0 or G > 0);
+ *   loss[0] = loss_weight * mean over the summed segments of class_weight[c] * loss_seg; with per_image that per image (an image
+ *   without a summed segment gives 0), then the mean (image_mean = 1) or the sum (0) over the B images.
+ *   logit (B,C,h,w); label (B,H,W) int64; slots: nslots DISTINCT classes in [0, C) on the device, or NULL (nslots = C);
+ *   class_weight C floats or NULL; B * H * W < 2^31, else RSCOTR_E_SHAPE.
+ *   _fwd writes lse (B,H,W), dplane (nslots, B*H*W) = d loss / d p_c at every valid pixel of every summed segment (other cells are
+ *     NOT written and never read), meta (nsegments + C ints: the summed flags, then the class -> slot table) and loss[0].  The
+ *     sort is a stable LSD radix sort, 4 passes of 8 bits over {0xFFFFFFFE - bits(e), pixel index | fg << 31} pairs, each pass
+ *     histogram / scan / scatter launches with grids fixed by the shape (a segment that is not summed leaves on the device flag);
+ *     then a foreground-count launch, the scan + closed-form gradient launch and a fold.  Integer LDS / global atomics only, float
+ *     sums in fixed order: bit-reproducible.  workspace: rscotr_upsample_lovasz_workspace(...) bytes, 16 per (slot, pixel) for the
+ *     two ping-pong {key, payload} pairs plus the histograms.
+ *   _bwd: dlogit (B,C,h,w) = grad_scale[0] * d(loss)/d(logit), grad_scale a DEVICE scalar: pix_s (B,H,W) = sum_slots p_c dplane
+ *     (the caller's scratch), then the gather of rscotr_upsample_ce_bwd with p_c (dplane_c - pix_s) over the non-ignored pixels;
+ *     cells no such pixel touches are written as exact zeros.
+ *   rscotr_upsample_lovasz_sort_tile / _sort_workgroup: the elements one wavefront / one workgroup of a sort pass ranks.
+ * No entry synchronises with the host or allocates: all of them can be captured in a hipGraph. */
+int64_t rscotr_upsample_lovasz_workspace(int B, int C, int nslots, int H, int W, int per_image);
+int rscotr_upsample_lovasz_sort_tile(void);
+int rscotr_upsample_lovasz_sort_workgroup(void);
+int rscotr_upsample_lovasz_fwd(const float* logit, const int64_t* label, const int* slots, const float* class_weight, float* lse,
+                               float* dplane, int* meta, float* loss, int B, int C, int nslots, int h, int w, int H, int W,
+                               int ignore_index, int present, int per_image, int image_mean, float loss_weight, float* workspace,
+                               int64_t workspace_bytes, void* stream);
+int rscotr_upsample_lovasz_bwd(const float* logit, const int64_t* label, const int* slots, const float* lse, const float* dplane,
+                               const int* meta, const float* grad_scale, float* pix_s, float* dlogit, int B, int C, int nslots,
+                               int h, int w, int H, int W, int ignore_index, int per_image, void* stream);
 
 /* Query position embedding of the DINO decoder (models/multi/bbox_head/transformer.py:43-76): pos (rows,4) = (x,y,w,h)
  * -> out (rows,512) = [emb(y)|emb(x)|emb(w)|emb(h)], emb(v)[2i] = sin(2 pi v / 10000^(2i/128)), [2i+1] = cos.  No

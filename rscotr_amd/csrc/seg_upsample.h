@@ -1,11 +1,13 @@
 // Bilinear resize (align_corners=False) for the fused seg losses (csrc/seg_loss.hip: cross-entropy, csrc/seg_dice.hip: Dice
-// and Tversky, csrc/seg_focal.hip: sigmoid focal) and the masked-attention mask: the source index, the 2 x 2 taps of an output
+// and Tversky, csrc/seg_focal.hip: sigmoid focal, csrc/seg_lovasz.hip: Lovasz-softmax) and the masked-attention mask: the source index, the 2 x 2 taps of an output
 // pixel, the blocked backward gather that every loss instantiates with its own gradient term, and the host helpers of their
 // entries.
 //
 // PyTorch's upsample_bilinear2d (align_corners=False) source index: s = max((d + 0.5) * in/out - 0.5, 0),
 // i0 = floor(s), i1 = min(i0 + 1, in - 1), lambda1 = s - i0.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace rscotr {
@@ -71,7 +73,14 @@ static_assert(2 * upsample_gather_lds_bytes(true) <= 160 * 1024, "two backward w
 //   int   stage(p, float& plane)          the label output pixel p is staged with, and its plane value (PLANE only)
 //   bool  skip(lab)                       a pixel staged with this label contributes nothing
 //   float term(prob, c, lab, plane)       the gradient term of class c from prob = softmax_c(p) (RAW: from u_c(p))
+//   static constexpr bool PIXEL           (optional, absent = false) term() takes the flat output-pixel index (b * H + y) * W + x
+//                                         as a fifth argument: a loss whose gradient reads a per-(class, pixel) plane (Lovasz)
 // Both implementations below — the staged walk and the one for footprints past UCE_FP — call the same stage / skip / term.
+template <class T, class = void>
+struct term_sees_pixel : std::false_type {};
+template <class T>
+struct term_sees_pixel<T, std::void_t<decltype(T::PIXEL)>> : std::bool_constant<T::PIXEL> {};
+
 template <class Term>
 __device__ __forceinline__ void upsample_gather(Term term, const float* __restrict__ logit, const float* __restrict__ lse,
                                                 const float* __restrict__ gscale, float* __restrict__ dlogit, int C, int h, int w,
@@ -193,7 +202,10 @@ __device__ __forceinline__ void upsample_gather(Term term, const float* __restri
               const float ls = __int_as_float(sc(ll.y));
               prob = __builtin_amdgcn_exp2f(fmaf(xl1, A1, fmaf(xl0, A0, -ls)));
             }
-            const float gq = term.term(prob, c, lab, Term::PLANE ? scf(pl) : 0.f);
+            float gq;
+            if constexpr (term_sees_pixel<Term>::value)
+              gq = term.term(prob, c, lab, Term::PLANE ? scf(pl) : 0.f, ((long)b * H + y_lo + r) * W + x_lo + xx);
+            else gq = term.term(prob, c, lab, Term::PLANE ? scf(pl) : 0.f);
             s0 = fmaf(xl0, gq, s0);
             s1 = fmaf(xl1, gq, s1);
           }
@@ -251,7 +263,9 @@ __device__ __forceinline__ void upsample_gather(Term term, const float* __restri
           float prob;
           if constexpr (Term::RAW) prob = v;
           else prob = __expf(v - lse[p]);
-          const float gq = term.term(prob, c, lab, plane);
+          float gq;
+          if constexpr (term_sees_pixel<Term>::value) gq = term.term(prob, c, lab, plane, p);
+          else gq = term.term(prob, c, lab, plane);
           t00 += yl0 * xl0 * gq; t01 += yl0 * xl1 * gq; t10 += yl1 * xl0 * gq; t11 += yl1 * xl1 * gq;
         }
         flush();

@@ -16,7 +16,7 @@ CPU tensor, or a non-zero return code raises.
     attention  swin_window_attention, mha (nn.MultiheadAttention), mask_logits, seg_class_logits, seg_attn_mask
     glue       level_embed_add, fan_out, cdn_queries, sine_embed4, neck im2col, layout helpers, cls pooling / loss
     losses     box utilities, match_cost_batched, lsap_*, focal / box loss sums, upsample_ce, upsample_ce_weighted, upsample_dice,
-               upsample_tversky, upsample_focal
+               upsample_tversky, upsample_focal, upsample_lovasz
     distutil   packed scalar all-reduces
     seg_eval   seg_predict (resample + flip + arg-max of the seg logits), seg_predict_tta (the same over V views: softmax, mean,
                arg-max), slide_windows / seg_predict_slide (test mode 'slide': the windows' logits merged, rescaled and arg-maxed),

@@ -1,6 +1,6 @@
 """Detection / segmentation loss pieces: box utilities, matching cost, the assignment solvers, focal / box loss sums, the
 fused upsample + cross-entropy (plain, and with class weights / avg_non_ignore / OHEM), the fused upsample + Dice / Tversky /
-sigmoid focal."""
+sigmoid focal / Lovasz-softmax."""
 import math
 
 import torch
@@ -492,6 +492,100 @@ def upsample_focal(seg_logit, label, ignore_index=255, gamma=2.0, alpha=0.5, cla
     H, W = label.shape[-2:]
     scale = float(loss_weight) / float(max(B * H * W * C, 1)) if reduction == 'mean' else float(loss_weight)
     return _UpsampleFocal.apply(seg_logit, label, ignore_index, gamma, alpha, alpha_c, class_weight, scale)
+
+
+class _UpsampleLovasz(Function):
+    """The fused bilinear upsample + softmax + Lovasz-softmax loss (rscotr_upsample_lovasz_*).  Forward leaves the per-pixel
+    log-sum-exp, the plane D (slots, B*H*W) = d loss / d p_c and the summed-segment flags; the upstream gradient meets them on the
+    device (grad_scale).  slots: an int32 device tensor of the summed classes or None (every class)."""
+
+    @staticmethod
+    def forward(ctx, logit, label, ignore_index, slots, present, per_image, image_mean, class_weight, loss_weight):
+        logit, label, cw, B, C, h, w, H, W, lse = _upsample_args(logit, label, class_weight)
+        _chk(slots)
+        dev = logit.device
+        nslots = C if slots is None else slots.numel()
+        nseg = B * nslots if per_image else nslots
+        dplane = torch.empty((nslots, B * H * W), dtype=torch.float32, device=dev)
+        meta = torch.empty(nseg + C, dtype=torch.int32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        nws = lib.rscotr_upsample_lovasz_workspace(B, C, nslots, H, W, int(per_image))
+        # the logits and lse, then per slot: {key, payload} written, 4 sort passes reading them twice and writing once, the scan
+        with _Prof('upsample_lovasz_fwd', 4 * B * C * h * w + 12 * B * H * W + (8 + 4 * 24 + 16) * nslots * B * H * W):
+            lib.call('rscotr_upsample_lovasz_fwd', logit.data_ptr(), label.data_ptr(), _ptr(slots), _ptr(cw), lse.data_ptr(),
+                     dplane.data_ptr(), meta.data_ptr(), loss.data_ptr(), B, C, nslots, h, w, H, W, int(ignore_index),
+                     int(present), int(per_image), int(image_mean), float(loss_weight), _WS.get(nws, dev).data_ptr(), nws,
+                     _stream())
+        ctx.save_for_backward(logit, label, lse, dplane, meta, slots)
+        ctx.opts = (int(ignore_index), nslots, int(per_image))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        logit, label, lse, dplane, meta, slots = ctx.saved_tensors
+        ignore, nslots, per_image = ctx.opts
+        B, C, h, w = logit.shape
+        H, W = label.shape[-2:]
+        gscale = g_loss.reshape(1).float().contiguous()
+        pix_s = torch.empty_like(lse)
+        dlogit = torch.empty_like(logit)
+        # pre-pass: logits, labels, lse and the slots' planes read, S written; gather: logits read, gradient written, labels, lse,
+        # S and the planes read
+        with _Prof('upsample_lovasz_bwd', 12 * B * C * h * w + (32 + 8 * nslots) * B * H * W):
+            lib.call('rscotr_upsample_lovasz_bwd', logit.data_ptr(), label.data_ptr(), _ptr(slots), lse.data_ptr(),
+                     dplane.data_ptr(), meta.data_ptr(), gscale.data_ptr(), pix_s.data_ptr(), dlogit.data_ptr(), B, C, nslots,
+                     h, w, H, W, ignore, per_image, _stream())
+        return dlogit, None, None, None, None, None, None, None, None
+
+
+# the elements one wavefront / one workgroup of a sort pass of csrc/seg_lovasz.hip ranks (rscotr_upsample_lovasz_sort_tile /
+# _sort_workgroup return the built values)
+LOVASZ_SORT_TILE, LOVASZ_SORT_WORKGROUP = 2048, 8192
+_lovasz_slots = {}  # (classes, device) -> int32 device tensor: a constant of the config, made once (also ahead of a capture)
+
+
+def upsample_lovasz(seg_logit, label, ignore_index=255, classes='present', per_image=False, class_weight=None, reduction='none',
+                    loss_weight=1.0):
+    """mmseg 0.28 LovaszLoss (loss_type='multi_class': lovasz_softmax) as BaseDecodeHead.losses reaches it, fused: bilinear resize
+    (align_corners=False) to the label size, softmax, and per summed class c over the pixels with label != ignore_index
+        fg = [label == c],  e = |fg - p_c| sorted descending (equal errors: ascending flat pixel index),
+        loss_c = sum_k e_(k) g_k,  g the discrete gradient of the Jaccard index along the sorted order (formed in closed form
+        from integer counts: 1 / U_k at a foreground element, I_k / (U_k (U_k - 1)) at a background one);
+        loss = loss_weight * mean_c class_weight[c] loss_c.
+    classes: 'present' (the classes with a foreground pixel), 'all', or a list of distinct class indices (absent ones included:
+    such a class costs its largest p_c).  per_image: the above per image, then reduction 'mean' or 'sum' over the images (an
+    image without a valid pixel gives 0 and counts); per_image=False takes reduction='none' only (the loss is a scalar already;
+    mmseg asserts the same).  A non-ignored label outside [0, C) is background for every class.  No valid pixel at all: 0.
+    Neither the up-sampled logits nor the probabilities are materialised; the ranking is a segmented stable radix sort on the
+    device (rscotr_upsample_lovasz_*): bit-reproducible, graph-capturable.  Memory: 20 bytes per (summed class slot, pixel) —
+    16 of workspace and the 4 of the saved gradient plane; `classes` as a list bounds it at wide heads.
+    seg_logit (B,C,h,w), label (B,H,W) int64, class_weight a float tensor / list of C entries or None -> loss 0-d."""
+    C = seg_logit.shape[1]
+    if C == 1:
+        raise ValueError('upsample_lovasz: the multi-class Lovasz loss needs more than one channel')
+    if per_image:
+        if reduction not in ('mean', 'sum'):
+            raise NotImplementedError(f"upsample_lovasz: per_image=True with reduction={reduction!r} is a vector loss (only "
+                                      "'mean' and 'sum')")
+    elif reduction != 'none':
+        raise NotImplementedError(f"upsample_lovasz: per_image=False with reduction={reduction!r}: write reduction='none' or "
+                                  'per_image=True (mmseg asserts the same)')
+    slots = None
+    if isinstance(classes, str):
+        if classes not in ('present', 'all'):
+            raise ValueError(f"upsample_lovasz: classes={classes!r} ('present', 'all' or a list of class indices)")
+    else:
+        cl = tuple(int(c) for c in classes)
+        if not cl or len(set(cl)) != len(cl) or min(cl) < 0 or max(cl) >= C:
+            raise ValueError(f'upsample_lovasz: classes={list(cl)!r} must be distinct indices in [0, {C})')
+        key = (cl, str(seg_logit.device))
+        slots = _lovasz_slots.get(key)
+        if slots is None:
+            slots = _lovasz_slots[key] = torch.tensor(cl, dtype=torch.int32, device=seg_logit.device)
+    if class_weight is not None and not torch.is_tensor(class_weight):
+        class_weight = torch.as_tensor(class_weight, dtype=torch.float32, device=seg_logit.device)
+    return _UpsampleLovasz.apply(seg_logit, label, ignore_index, slots, classes == 'present', bool(per_image),
+                                 reduction == 'mean', class_weight, loss_weight)
 
 
 class _DetProposals(Function):

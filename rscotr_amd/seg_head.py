@@ -172,8 +172,57 @@ class FocalLoss(nn.Module):
                                   loss_weight=self.loss_weight)
 
 
+@MODELS.register_module()
+class LovaszLoss(nn.Module):
+    """mmseg 0.28 LovaszLoss, loss_type='multi_class', as the seg head uses it: the options are stored here and applied by the
+    fused kernels (ops.upsample_lovasz) with the HEAD's ignore_index, as BaseDecodeHead.losses passes it (like FocalLoss); the
+    sampler's `weight` is swallowed, as mmseg's Lovasz ignores it (like DiceLoss).  classes: 'present', 'all' or a list of class
+    indices; per_image=False takes reduction='none' (mmseg's constructor asserts the same, so the default-argument
+    dict(type='LovaszLoss') is refused), per_image=True takes 'mean' or 'sum' over the images.
+    Memory: the device sort holds two ping-pong (key, payload) pairs and the gradient plane per summed class slot, 20 bytes per
+    (slot, pixel): 73 MB at 7 classes and 2 x 512 x 512, about 1 GB at a 100-channel head unless `classes` lists the few classes
+    to sum (classes=[0, 1, 2, 3, 4, 5]: 63 MB).  No parameters, no buffers: the state dict keeps the reference's keys."""
+
+    def __init__(self, loss_type='multi_class', classes='present', per_image=False, reduction='mean', class_weight=None,
+                 loss_weight=1.0, loss_name='loss_lovasz'):
+        super().__init__()
+        if loss_type != 'multi_class':
+            raise NotImplementedError(f"LovaszLoss: loss_type={loss_type!r} (only 'multi_class': the binary hinge form is not "
+                                      'implemented)')
+        if reduction not in ('mean', 'sum', 'none'):
+            raise ValueError(f"LovaszLoss: reduction={reduction!r} (one of 'mean', 'sum', 'none')")
+        if per_image and reduction == 'none':
+            raise NotImplementedError("LovaszLoss: per_image=True with reduction='none' is a vector loss (only 'mean' and 'sum')")
+        if not per_image and reduction != 'none':
+            raise NotImplementedError(f"LovaszLoss: per_image=False with reduction={reduction!r}: mmseg's own constructor "
+                                      "asserts there; write reduction='none' or per_image=True")
+        if isinstance(classes, str):
+            if classes not in ('present', 'all'):
+                raise ValueError(f"LovaszLoss: classes={classes!r} ('present', 'all' or a list of class indices)")
+        elif isinstance(classes, (list, tuple)) and classes and all(isinstance(c, int) and not isinstance(c, bool) for c in classes):
+            classes = [int(c) for c in classes]
+            if len(set(classes)) != len(classes) or min(classes) < 0:
+                raise ValueError(f'LovaszLoss: classes={classes!r} must be distinct non-negative class indices')
+        else:
+            raise TypeError(f"LovaszLoss: classes must be 'present', 'all' or a non-empty list of ints, got {classes!r}")
+        self.loss_type, self.classes, self.per_image, self.reduction = loss_type, classes, bool(per_image), reduction
+        self.class_weight = _class_weight_list(class_weight)
+        self.loss_weight, self.loss_name = float(loss_weight), loss_name
+        self._cw = {}
+
+    def weight_on(self, device, num_channels):
+        return _class_weight_on(self, device, num_channels)
+
+    def forward(self, seg_logit, label, ignore_index=255, **kwargs):
+        """seg_logit (B,C,h,w) at the head's resolution, label (B,H,W) int64 -> loss_weight * lovasz (0-d)."""
+        cw = self.weight_on(seg_logit.device, seg_logit.shape[1])
+        return ops.upsample_lovasz(seg_logit, label, ignore_index, classes=self.classes, per_image=self.per_image,
+                                   class_weight=cw, reduction=self.reduction, loss_weight=self.loss_weight)
+
+
 # the types a seg head's loss_decode entries resolve to (every one but the first as an entry of a list only)
-_SEG_LOSSES = {'CrossEntropyLoss': CrossEntropyLoss, 'DiceLoss': DiceLoss, 'FocalLoss': FocalLoss, 'TverskyLoss': TverskyLoss}
+_SEG_LOSSES = {'CrossEntropyLoss': CrossEntropyLoss, 'DiceLoss': DiceLoss, 'FocalLoss': FocalLoss, 'TverskyLoss': TverskyLoss,
+               'LovaszLoss': LovaszLoss}
 
 
 def _build_seg_loss(cfg):
@@ -315,7 +364,7 @@ class Mask2FormerHead(nn.Module):
         # a dict or a list of dicts, as mmseg's BaseDecodeHead takes it (mask2former_head.py:85-93); no parameters, no keys
         # The single-dict form stays what it was, one CrossEntropyLoss; a DiceLoss is an entry of a loss_decode LIST (next to a
         # CrossEntropyLoss entry as in mmseg's documented pair, or on its own: [dict(type='DiceLoss')])
-        # FocalLoss and TverskyLoss are list entries like DiceLoss.  The entry types resolve through _SEG_LOSSES: 'FocalLoss' in
+        # FocalLoss, TverskyLoss and LovaszLoss are list entries like DiceLoss.  The entry types resolve through _SEG_LOSSES: 'FocalLoss' in
         # MODELS is the det head's holder
         is_list = isinstance(loss_decode, (list, tuple))
         cfgs = list(loss_decode) if is_list else [loss_decode]
@@ -327,7 +376,7 @@ class Mask2FormerHead(nn.Module):
                     raise NotImplementedError(f"loss_decode type {name!r} as a single dict: {name} is taken as an entry of a "
                                               f"loss_decode list, e.g. [dict(type='CrossEntropyLoss'), dict(type={name!r})]")
                 raise NotImplementedError(f'loss_decode type {name!r}: the fused seg losses implement CrossEntropyLoss, and DiceLoss, '
-                                          'FocalLoss and TverskyLoss as entries of a list, only')
+                                          'FocalLoss, TverskyLoss and LovaszLoss as entries of a list, only')
         built = [_build_seg_loss(c) for c in cfgs]
         self.loss_decode = nn.ModuleList(built) if isinstance(loss_decode, (list, tuple)) else built[0]
         if sampler is not None and any(isinstance(ld, FocalLoss) for ld in built):
@@ -426,14 +475,14 @@ class Mask2FormerHead(nn.Module):
         ce = [ld for ld in entries if isinstance(ld, CrossEntropyLoss)]
         if len(ce) == len(entries):
             return self._ce_losses(ce, seg_logit, seg_label)
-        # a list with DiceLoss / TverskyLoss / FocalLoss entries: the cross-entropy entries take the path they take alone; every
-        # other entry is one fused call (the sampler's mask and the head's ignore_index do not reach a Dice or Tversky entry, as
-        # in mmseg; a Focal entry takes the head's ignore_index); entries of one name add up
+        # a list with DiceLoss / TverskyLoss / FocalLoss / LovaszLoss entries: the cross-entropy entries take the path they take
+        # alone; every other entry is one fused call (the sampler's mask and the head's ignore_index do not reach a Dice or
+        # Tversky entry, as in mmseg; a Focal or Lovasz entry takes the head's ignore_index); entries of one name add up
         out = self._ce_losses(ce, seg_logit, seg_label) if ce else {}
         acc_seg = out.pop('acc_seg', None)
         label = seg_label.squeeze(1)
         for ld in entries:
-            if isinstance(ld, (DiceLoss, TverskyLoss, FocalLoss)):
+            if isinstance(ld, (DiceLoss, TverskyLoss, FocalLoss, LovaszLoss)):
                 loss = ld(seg_logit, label, ignore_index=self.ignore_index)
                 out[ld.loss_name] = out[ld.loss_name] + loss if ld.loss_name in out else loss
         if acc_seg is None:  # no cross-entropy entry: mmseg reports the accuracy all the same
