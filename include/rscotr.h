@@ -34,7 +34,8 @@ extern "C" {
  * argument list, so they keep 11: a library without them fails to bind by name; the seg head's scheme-1 entries rscotr_seg_mix_* and
  * the det input chain rscotr_img_aug_chain_u8 likewise, and the Dice, Tversky, focal and Lovasz seg losses
  * rscotr_upsample_dice_* / rscotr_upsample_tversky_* / rscotr_upsample_focal_* / rscotr_upsample_lovasz_*, and the rotation input entries
- * rscotr_img_aug_rot_u8 / rscotr_seg_label_rot_u8).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
+ * rscotr_img_aug_rot_u8 / rscotr_seg_label_rot_u8, and the det loss entries rscotr_match_cost_kind / rscotr_box_loss_kind /
+ * rscotr_qfl_sum).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
  * its first call (rscotr_amd/_lib.py does) — a stale .so would take a stream handle for a pointer. */
 #define RSCOTR_ABI_VERSION 11
 int rscotr_version(void);
@@ -732,7 +733,18 @@ int rscotr_seg_mix_bwd(const float* g, const float* cls, const float* e, const f
  * rscotr_focal_sum: mmcv sigmoid_focal_loss summed per set (detr_head.py:384-385, dino_head.py:272-273): pred (S,N,C),
  * target (S,N) int64 in [0,C] (C = background), weight (S,N) or NULL -> sums (S) and dpred (S,N,C) = d sums / d pred.
  * rscotr_box_loss: L1 (cxcywh, normalised; weight (S,B,Q,4)) and GIoU (xyxy * factors, eps; weight = mean of the 4)
- * sums per set (detr_head.py:392-415): sums (2,S) = {l1, giou}; d_l1, d_giou (S,B,Q,4) = their gradients wrt pred. */
+ * sums per set (detr_head.py:392-415): sums (2,S) = {l1, giou}; d_l1, d_giou (S,B,Q,4) = their gradients wrt pred.
+ * The three entries above are the default recipe; the _kind entries below take mmdet's other choices and, given the
+ * default's, launch the same kernels (bit-identical results):
+ * rscotr_match_cost_kind: iou_mode 0 = 'giou', 1 = 'iou' (cost = -ov / max(union, 1e-6) * w_iou) of IoUCost.
+ * rscotr_box_loss_kind: kind 0 = GIoULoss, 1 = IoULoss (iou = max(ov / max(union, 1e-6), eps); mode 0 = 1 - iou, 1 = 1 - iou^2,
+ * 2 = -log iou), 2 = DIoULoss (1 - ov / (union + eps) + rho2 / (cw^2 + ch^2 + eps)), 3 = CIoULoss (DIoU's terms and
+ * alpha v, v = 4 / pi^2 (atan(w2 / (h2 + eps)) - atan(w1 / (h1 + eps)))^2, alpha = [iou > 0.5] v / (1 - iou + v) held constant, the
+ * measure clamped to [-1, 1]); mode is read by kind 1 only.  sums[1] and d_iou hold the chosen loss; a row whose weights are
+ * all 0 adds an exact 0 and gets a zero gradient whatever its boxes hold.
+ * rscotr_qfl_sum: mmdet QualityFocalLoss summed per set in the layout of rscotr_focal_sum; the quality of a foreground row is
+ * the IoU (union clamped at 1e-6) of box and box_target (S,N,4), both cxcywh normalised, and is a constant: BCE(x, 0) sigma^beta
+ * off the target class, BCE(x, s) |s - sigma|^beta at it -> sums (S), dpred (S,N,C).  The boxes get no gradient. */
 /* out = sigmoid(delta + inverse_sigmoid(ref, eps)) — the box refinement step of the DINO decoder / head
  * (bbox_head/transformer.py:112-118, dino_head.py:133-137) — and its backward (d_delta / d_ref may be NULL). */
 int rscotr_refine_box_fwd(const float* delta, const float* ref, float* out, int64_t n, float eps, void* stream);
@@ -745,6 +757,13 @@ int rscotr_focal_sum(const float* pred, const int64_t* target, const float* weig
                      int N, int C, float gamma, float alpha, void* stream);
 int rscotr_box_loss(const float* pred, const float* target, const float* weight, const float* factors, float* sums,
                     float* d_l1, float* d_giou, int S, int B, int Q, float eps, void* stream);
+int rscotr_match_cost_kind(const float* cls, const float* box, const float* gt_box, const int64_t* gt_lab,
+                           const float* factors, float* cost, int S, int B, int Q, int C, int G, float w_cls, float w_l1,
+                           float w_iou, float alpha, float gamma, float eps, int iou_mode, void* stream);
+int rscotr_box_loss_kind(const float* pred, const float* target, const float* weight, const float* factors, float* sums,
+                         float* d_l1, float* d_iou, int S, int B, int Q, float eps, int kind, int mode, void* stream);
+int rscotr_qfl_sum(const float* pred, const int64_t* target, const float* weight, const float* box, const float* box_target,
+                   float* sums, float* dpred, int S, int N, int C, float beta, void* stream);
 
 /* ---- Hungarian matching (host, fp64) ---------------------------------------------------------
  * Replaces scipy.optimize.linear_sum_assignment as called by mmdet HungarianAssigner.assign,

@@ -21,7 +21,9 @@ HOST_FLAGS = ["-ffp-contract=off"]
 # Kernels that fit their register budget with little to spare (csrc/gemm_split_body.h, h3_two_tiles: 246 - 249 of 256 VGPRs at two
 # wavefronts per SIMD): their sources are compiled with the resource-usage remark, and the build fails if one of them spills.
 REMARK_FLAGS = ["-Rpass-analysis=kernel-resource-usage"]
-NO_SCRATCH = {"gemm_h3.hip": ("gemm_h3_128_kernel",), "gemm_group.hip": ("gemm_h3_group_kernel",)}
+# (det_loss.hip: the per-kind box losses carry a gradient per corner through the IoU terms — CIoU's is the widest)
+NO_SCRATCH = {"gemm_h3.hip": ("gemm_h3_128_kernel",), "gemm_group.hip": ("gemm_h3_group_kernel",),
+              "det_loss.hip": ("box_loss_kernel", "match_cost_kernel", "qfl_sum_kernel")}
 
 
 def scratch_report(remarks, names):

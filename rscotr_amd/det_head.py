@@ -28,7 +28,8 @@ FP32_EPS = float(torch.finfo(torch.float32).eps)
 
 
 # ------------------------------------------------------------------------------------------
-# loss / assigner config holders (mmdet FocalLoss, L1Loss, GIoULoss, HungarianAssigner + costs)
+# loss / assigner config holders (mmdet FocalLoss / QualityFocalLoss, L1Loss, GIoULoss / IoULoss / DIoULoss / CIoULoss,
+# HungarianAssigner + costs)
 # ------------------------------------------------------------------------------------------
 @MODELS.register_module()
 class FocalLoss(nn.Module):
@@ -47,9 +48,76 @@ class L1Loss(nn.Module):
 
 @MODELS.register_module()
 class GIoULoss(nn.Module):
+    kind = 'giou'  # ops.box_loss_sums: the default recipe's own launch
+
     def __init__(self, eps=1e-6, reduction='mean', loss_weight=1.0):
         super().__init__()
         self.eps, self.loss_weight = eps, loss_weight
+
+
+def _mean_only(name, reduction):
+    if reduction != 'mean':
+        raise NotImplementedError(f"{name}: reduction={reduction!r} is not implemented (the DETR heads normalise the summed loss "
+                                  f"by their own factor: 'mean')")
+
+
+@MODELS.register_module()
+class IoULoss(nn.Module):
+    """mmdet IoULoss: 1 - iou | 1 - iou^2 | -log(iou) of iou = max(IoU, eps) (ops.box_loss_sums_kind, kind 'iou')."""
+    kind = 'iou'
+
+    def __init__(self, linear=False, eps=1e-6, reduction='mean', loss_weight=1.0, mode='log'):
+        super().__init__()
+        _mean_only('IoULoss', reduction)
+        if mode not in ('linear', 'square', 'log'):
+            raise NotImplementedError(f"IoULoss: mode={mode!r} is not implemented ('linear', 'square', 'log')")
+        self.mode = 'linear' if linear else mode
+        self.eps, self.loss_weight = eps, loss_weight
+
+
+@MODELS.register_module()
+class DIoULoss(nn.Module):
+    """mmdet DIoULoss: 1 - IoU + centre distance^2 / enclosing diagonal^2 (ops.box_loss_sums_kind, kind 'diou')."""
+    kind = 'diou'
+
+    def __init__(self, eps=1e-6, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        _mean_only('DIoULoss', reduction)
+        self.eps, self.loss_weight = eps, loss_weight
+
+
+@MODELS.register_module()
+class CIoULoss(nn.Module):
+    """mmdet CIoULoss: DIoU's terms and the aspect-ratio term alpha v (ops.box_loss_sums_kind, kind 'ciou')."""
+    kind = 'ciou'
+
+    def __init__(self, eps=1e-6, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        _mean_only('CIoULoss', reduction)
+        self.eps, self.loss_weight = eps, loss_weight
+
+
+@MODELS.register_module()
+class BoundedIoULoss(nn.Module):
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError("loss_iou type 'BoundedIoULoss' is not implemented (GIoULoss, IoULoss, DIoULoss, CIoULoss are)")
+
+
+@MODELS.register_module()
+class QualityFocalLoss(nn.Module):
+    """mmdet QualityFocalLoss as loss_cls of the DETR / DINO heads of mmdet 3.x: the target of a foreground query's class is the
+    IoU of its (detached) predicted box with its target box (ops.quality_focal_loss_sum)."""
+
+    def __init__(self, use_sigmoid=True, beta=2.0, reduction='mean', loss_weight=1.0, activated=False):
+        super().__init__()
+        if not use_sigmoid:
+            raise NotImplementedError('QualityFocalLoss: use_sigmoid=False is not implemented (mmdet supports the sigmoid form only)')
+        if activated:
+            raise NotImplementedError('QualityFocalLoss: activated=True is not implemented (the head passes logits)')
+        _mean_only('QualityFocalLoss', reduction)
+        if not beta >= 0:
+            raise ValueError(f'QualityFocalLoss: beta must be >= 0, got {beta}')
+        self.use_sigmoid, self.beta, self.loss_weight = use_sigmoid, float(beta), loss_weight
 
 
 @MODELS.register_module()
@@ -57,7 +125,9 @@ class HungarianAssigner:
     def __init__(self, cls_cost=dict(type='ClassificationCost', weight=1.), reg_cost=dict(type='BBoxL1Cost', weight=1.0),
                  iou_cost=dict(type='IoUCost', iou_mode='giou', weight=1.0)):
         assert cls_cost['type'] == 'FocalLossCost' and reg_cost['type'] == 'BBoxL1Cost' and iou_cost['type'] == 'IoUCost'
-        assert reg_cost.get('box_format', 'xyxy') == 'xywh' and iou_cost.get('iou_mode', 'giou') == 'giou'
+        assert reg_cost.get('box_format', 'xyxy') == 'xywh'
+        self.iou_mode = iou_cost.get('iou_mode', 'giou')
+        assert self.iou_mode in ('giou', 'iou'), f"IoUCost: iou_mode must be 'giou' or 'iou', got {self.iou_mode!r}"
         self.w_cls, self.w_l1, self.w_iou = cls_cost.get('weight', 1.), reg_cost.get('weight', 1.), iou_cost.get('weight', 1.)
         self.alpha, self.gamma, self.eps = cls_cost.get('alpha', 0.25), cls_cost.get('gamma', 2.0), cls_cost.get('eps', 1e-12)
 
@@ -746,8 +816,12 @@ class DINOHead(nn.Module):
         box_sets = torch.cat([enc_topk_anchors[None], m_box], 0)
         S, G = nl + 1, st.gcap
         a = self.assigner
-        cost = ops.match_cost_batched(cls_sets.detach(), box_sets.detach(), t['gt_box'], t['gt_lab'], t['factors'],
-                                      a.w_cls, a.w_l1, a.w_iou, a.alpha, a.gamma, a.eps)
+        if a.iou_mode == 'giou':
+            cost = ops.match_cost_batched(cls_sets.detach(), box_sets.detach(), t['gt_box'], t['gt_lab'], t['factors'],
+                                          a.w_cls, a.w_l1, a.w_iou, a.alpha, a.gamma, a.eps)
+        else:
+            cost = ops.match_cost_batched_kind(cls_sets.detach(), box_sets.detach(), t['gt_box'], t['gt_lab'], t['factors'],
+                                               a.w_cls, a.w_l1, a.w_iou, a.alpha, a.gamma, a.eps, a.iou_mode)
         gcount_s = t['gcount_s'] if 'gcount_s' in t else t['gcount'].repeat(S)
         qfg = ops.lsap_device(cost.reshape(S * B, Q, G), gcount_s).view(S, B, G)
         if record is not None:
@@ -921,7 +995,8 @@ class DINOHead(nn.Module):
             if G == 0:
                 continue
             c = ops.match_cost(cls_sets[:, i].detach(), box_sets[:, i].detach(), gt_bboxes[i], gt_labels[i], iw, ih,
-                               a.w_cls, a.w_l1, a.w_iou, a.alpha, a.gamma, a.eps)  # (S,Q,G)
+                               a.w_cls, a.w_l1, a.w_iou, a.alpha, a.gamma, a.eps,
+                               **({} if a.iou_mode == 'giou' else dict(iou_mode=a.iou_mode)))  # (S,Q,G)
             costs.append(c.reshape(-1))
             rows += [Q] * S
             cols += [G] * S
@@ -957,26 +1032,41 @@ class DINOHead(nn.Module):
         S, B, Q, C = cls_sets.shape
         if scales is not None:
             assert Q > 0
-            raw_cls = ops.sigmoid_focal_loss_sum(cls_sets.reshape(S, B * Q, C), labels.reshape(S, B * Q),
-                                                 self.loss_cls.gamma, self.loss_cls.alpha,
-                                                 None if cls_weight is None else cls_weight.reshape(S, B * Q))
-            l1, gi = ops.box_loss_sums(box_sets, bbox_targets, bbox_weights, factors.view(B, 4), self.loss_iou.eps)
+            raw_cls = self._cls_sums(cls_sets, box_sets, labels, bbox_targets, cls_weight)
+            l1, gi = self._box_sums(box_sets, bbox_targets, bbox_weights, factors.view(B, 4))
             return torch.stack([raw_cls, l1, gi], 1) * scales
         cls_avg = ops.clamp_min(cls_avg, 1)
         if Q > 0:
-            loss_cls = ops.sigmoid_focal_loss_sum(cls_sets.reshape(S, B * Q, C), labels.reshape(S, B * Q),
-                                                  self.loss_cls.gamma, self.loss_cls.alpha,
-                                                  None if cls_weight is None else cls_weight.reshape(S, B * Q))
+            loss_cls = self._cls_sums(cls_sets, box_sets, labels, bbox_targets, cls_weight)
             loss_cls = loss_cls * (self.loss_cls.loss_weight / (cls_avg + FP32_EPS))
         else:
             loss_cls = cls_sets.new_zeros(S)
         npos = ops.clamp_min(npos, 1.0)
         if factors is None:
             factors = cls_sets.new_tensor([[w, h, w, h] for (h, w) in img_shapes])
-        l1, gi = ops.box_loss_sums(box_sets, bbox_targets, bbox_weights, factors.view(B, 4), self.loss_iou.eps)
+        l1, gi = self._box_sums(box_sets, bbox_targets, bbox_weights, factors.view(B, 4))
         loss_iou = gi * (self.loss_iou.loss_weight / (npos + FP32_EPS))
         loss_bbox = l1 * (self.loss_bbox.loss_weight / (npos + FP32_EPS))
         return loss_cls, loss_bbox, loss_iou
+
+    def _cls_sums(self, cls_sets, box_sets, labels, bbox_targets, cls_weight):
+        """Per-set sums of loss_cls: FocalLoss (the default recipe's launch) or QualityFocalLoss, whose target score is the IoU
+        of a foreground query's detached box with its target box."""
+        S, B, Q, C = cls_sets.shape
+        w = None if cls_weight is None else cls_weight.reshape(S, B * Q)
+        if isinstance(self.loss_cls, QualityFocalLoss):
+            return ops.quality_focal_loss_sum(cls_sets.reshape(S, B * Q, C), labels.reshape(S, B * Q),
+                                              box_sets.detach().reshape(S, B * Q, 4), bbox_targets.reshape(S, B * Q, 4),
+                                              self.loss_cls.beta, w)
+        return ops.sigmoid_focal_loss_sum(cls_sets.reshape(S, B * Q, C), labels.reshape(S, B * Q),
+                                          self.loss_cls.gamma, self.loss_cls.alpha, w)
+
+    def _box_sums(self, box_sets, bbox_targets, bbox_weights, factors):
+        """Per-set sums of loss_bbox (L1) and loss_iou: GIoULoss (the default recipe's launch) or the holder's kind."""
+        li = self.loss_iou
+        if li.kind == 'giou':
+            return ops.box_loss_sums(box_sets, bbox_targets, bbox_weights, factors, li.eps)
+        return ops.box_loss_sums_kind(box_sets, bbox_targets, bbox_weights, factors, li.kind, li.eps, getattr(li, 'mode', 'log'))
 
     def loss(self, all_cls_scores, all_bbox_preds, enc_topk_scores, enc_topk_anchors, gt_bboxes_list, gt_labels_list,
              img_metas, dn_meta=None, gt_bboxes_ignore=None, record=None):

@@ -15,7 +15,7 @@ CPU tensor, or a non-zero return code raises.
     deform     msda, msda_prep, msda_attention (mmcv MultiScaleDeformableAttention)
     attention  swin_window_attention, mha (nn.MultiheadAttention), mask_logits, seg_class_logits, seg_attn_mask
     glue       level_embed_add, fan_out, cdn_queries, sine_embed4, neck im2col, layout helpers, cls pooling / loss
-    losses     box utilities, match_cost_batched, lsap_*, focal / box loss sums, upsample_ce, upsample_ce_weighted, upsample_dice,
+    losses     box utilities, match_cost_batched(_kind), lsap_*, focal / quality focal / box loss sums (box_loss_sums_kind), upsample_ce, upsample_ce_weighted, upsample_dice,
                upsample_tversky, upsample_focal, upsample_lovasz
     distutil   packed scalar all-reduces
     seg_eval   seg_predict (resample + flip + arg-max of the seg logits), seg_predict_tta (the same over V views: softmax, mean,

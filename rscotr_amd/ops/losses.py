@@ -1,4 +1,5 @@
-"""Detection / segmentation loss pieces: box utilities, matching cost, the assignment solvers, focal / box loss sums, the
+"""Detection / segmentation loss pieces: box utilities, matching cost (giou / iou), the assignment solvers, focal / quality focal /
+box loss sums (GIoU, and the IoU / DIoU / CIoU kinds), the
 fused upsample + cross-entropy (plain, and with class weights / avg_non_ignore / OHEM), the fused upsample + Dice / Tversky /
 sigmoid focal / Lovasz-softmax."""
 import math
@@ -40,9 +41,25 @@ def _giou(b1, b2, aligned, eps=1e-6):
     return ious - (earea - union) / earea
 
 
-def match_cost(cls_score, bbox_pred, gt_bboxes, gt_labels, img_w, img_h, w_cls, w_l1, w_iou, alpha, gamma, eps):
-    """mmdet FocalLossCost + BBoxL1Cost(xywh) + IoUCost(giou) for S prediction sets of one image:
+def _iou(b1, b2, eps=1e-6):
+    """mmdet bbox_overlaps(mode='iou') of every box of b1 (..., N, 4) against every box of b2 (..., M, 4), xyxy."""
+    area1 = (b1[..., 2] - b1[..., 0]) * (b1[..., 3] - b1[..., 1])
+    area2 = (b2[..., 2] - b2[..., 0]) * (b2[..., 3] - b2[..., 1])
+    wh = (torch.min(b1[..., :, None, 2:], b2[..., None, :, 2:]) - torch.max(b1[..., :, None, :2], b2[..., None, :, :2])).clamp(min=0)
+    overlap = wh[..., 0] * wh[..., 1]
+    return overlap / (area1[..., None] + area2[..., None, :] - overlap).clamp(min=eps)
+
+
+IOU_MODES = {'giou': 0, 'iou': 1}                     # IoUCost's iou_mode -> rscotr_match_cost_kind
+BOX_KINDS = {'giou': 0, 'iou': 1, 'diou': 2, 'ciou': 3}  # loss_iou holder -> rscotr_box_loss_kind
+IOU_LOSS_MODES = {'linear': 0, 'square': 1, 'log': 2}  # IoULoss's mode
+
+
+def match_cost(cls_score, bbox_pred, gt_bboxes, gt_labels, img_w, img_h, w_cls, w_l1, w_iou, alpha, gamma, eps, iou_mode='giou'):
+    """mmdet FocalLossCost + BBoxL1Cost(xywh) + IoUCost(iou_mode: 'giou' | 'iou') for S prediction sets of one image:
     cls_score (S,Q,C), bbox_pred (S,Q,4) cxcywh normalised, gt (G,4) xyxy pixels -> (S,Q,G)."""
+    if iou_mode not in IOU_MODES:
+        raise ValueError(f'match_cost: iou_mode must be one of {sorted(IOU_MODES)}, got {iou_mode!r}')
     factor = gt_bboxes.new_tensor([img_w, img_h, img_w, img_h])
     p = cls_score.sigmoid()
     neg = -(1 - p + eps).log() * (1 - alpha) * p.pow(gamma)
@@ -51,7 +68,8 @@ def match_cost(cls_score, bbox_pred, gt_bboxes, gt_labels, img_w, img_h, w_cls, 
     gt_c = bbox_xyxy_to_cxcywh(gt_bboxes / factor)
     c_l1 = (bbox_pred[..., :, None, :] - gt_c[None, None, :, :]).abs().sum(-1) * w_l1
     boxes = bbox_cxcywh_to_xyxy(bbox_pred) * factor
-    c_iou = -_giou(boxes, gt_bboxes.unsqueeze(0).expand(boxes.shape[0], -1, -1), aligned=False) * w_iou
+    gts = gt_bboxes.unsqueeze(0).expand(boxes.shape[0], -1, -1)
+    c_iou = -(_giou(boxes, gts, aligned=False) if iou_mode == 'giou' else _iou(boxes, gts)) * w_iou
     return c_cls + c_l1 + c_iou
 
 
@@ -69,6 +87,24 @@ def match_cost_batched(cls_score, bbox_pred, gt_bboxes, gt_labels, factors, w_cl
     lib.call('rscotr_match_cost', cls_score.data_ptr(), bbox_pred.data_ptr(), gt_bboxes.data_ptr(), gt_labels.data_ptr(),
              factors.data_ptr(), cost.data_ptr(), S, B, Q, C, G, float(w_cls), float(w_l1), float(w_iou), float(alpha),
              float(gamma), float(eps), _stream())
+    return cost
+
+
+def match_cost_batched_kind(cls_score, bbox_pred, gt_bboxes, gt_labels, factors, w_cls, w_l1, w_iou, alpha, gamma, eps,
+                            iou_mode='giou'):
+    """match_cost_batched with IoUCost's iou_mode chosen ('giou' | 'iou': cost = -IoU * w_iou, union clamped at 1e-6), one
+    kernel (rscotr_match_cost_kind); 'giou' launches match_cost_batched's kernel."""
+    if iou_mode not in IOU_MODES:
+        raise ValueError(f'match_cost_batched_kind: iou_mode must be one of {sorted(IOU_MODES)}, got {iou_mode!r}')
+    cls_score, bbox_pred, gt_bboxes, factors = _f32c(cls_score), _f32c(bbox_pred), _f32c(gt_bboxes), _f32c(factors)
+    gt_labels = gt_labels.contiguous()
+    _chk(cls_score, bbox_pred, gt_bboxes, gt_labels, factors)
+    S, B, Q, C = cls_score.shape
+    G = gt_bboxes.shape[1]
+    cost = torch.empty((S, B, Q, G), dtype=torch.float32, device=cls_score.device)
+    lib.call('rscotr_match_cost_kind', cls_score.data_ptr(), bbox_pred.data_ptr(), gt_bboxes.data_ptr(), gt_labels.data_ptr(),
+             factors.data_ptr(), cost.data_ptr(), S, B, Q, C, G, float(w_cls), float(w_l1), float(w_iou), float(alpha),
+             float(gamma), float(eps), IOU_MODES[iou_mode], _stream())
     return cost
 
 
@@ -188,6 +224,71 @@ def box_loss_sums(pred, target, weight, factors, eps=1e-6):
     (detr_head.py:392-415), one kernel that also leaves both gradients (rscotr_box_loss):
     pred / target / weight (S,B,Q,4) -> (l1 (S,), giou (S,)); the GIoU weight is the mean of the 4 box weights."""
     return _BoxLoss.apply(pred, target, weight, factors, eps)
+
+
+class _BoxLossKind(Function):
+    @staticmethod
+    def forward(ctx, pred, target, weight, factors, eps, kind, mode):
+        pred, target, weight, factors = _f32c(pred), _f32c(target), _f32c(weight), _f32c(factors)
+        _chk(pred, target, weight, factors)
+        S, B, Q, _ = pred.shape
+        sums = torch.empty((2, S), dtype=torch.float32, device=pred.device)
+        d_l1, d_iou = torch.empty_like(pred), torch.empty_like(pred)
+        lib.call('rscotr_box_loss_kind', pred.data_ptr(), target.data_ptr(), weight.data_ptr(), factors.data_ptr(),
+                 sums.data_ptr(), d_l1.data_ptr(), d_iou.data_ptr(), S, B, Q, float(eps), kind, mode, _stream())
+        ctx.save_for_backward(d_l1, d_iou)
+        return sums[0], sums[1]
+
+    @staticmethod
+    def backward(ctx, g1, g2):
+        d_l1, d_iou = ctx.saved_tensors
+        return d_l1 * g1.view(-1, 1, 1, 1) + d_iou * g2.view(-1, 1, 1, 1), None, None, None, None, None, None
+
+
+def box_loss_sums_kind(pred, target, weight, factors, kind='giou', eps=1e-6, mode='log'):
+    """box_loss_sums with the IoU loss chosen: kind 'giou' | 'iou' | 'diou' | 'ciou' = mmdet GIoULoss / IoULoss / DIoULoss /
+    CIoULoss on the pixel boxes; `mode` ('linear' | 'square' | 'log') is IoULoss's and read by kind 'iou' only.  One kernel
+    that also leaves both gradients (rscotr_box_loss_kind; 'giou' launches box_loss_sums' kernel) -> (l1 (S,), iou loss (S,)).
+    A row whose four weights are 0 adds an exact 0 and gets a zero gradient."""
+    if kind not in BOX_KINDS:
+        raise ValueError(f'box_loss_sums_kind: kind must be one of {sorted(BOX_KINDS)}, got {kind!r}')
+    if mode not in IOU_LOSS_MODES:
+        raise ValueError(f'box_loss_sums_kind: mode must be one of {sorted(IOU_LOSS_MODES)}, got {mode!r}')
+    return _BoxLossKind.apply(pred, target, weight, factors, eps, BOX_KINDS[kind], IOU_LOSS_MODES[mode])
+
+
+class _QFLSum(Function):
+    @staticmethod
+    def forward(ctx, pred, target, box_pred, box_target, beta, weight):
+        pred, box_pred, box_target = _f32c(pred), _f32c(box_pred.detach()), _f32c(box_target)
+        target = target.contiguous()
+        weight = None if weight is None else _f32c(weight)
+        _chk(pred, target, box_pred, box_target, weight)
+        S, N, C = pred.shape
+        if tuple(box_pred.shape) != (S, N, 4) or tuple(box_target.shape) != (S, N, 4) or tuple(target.shape) != (S, N):
+            raise ValueError(f'quality_focal_loss_sum: pred {tuple(pred.shape)} needs target (S,N) and boxes (S,N,4), got '
+                             f'{tuple(target.shape)}, {tuple(box_pred.shape)}, {tuple(box_target.shape)}')
+        sums = torch.empty(S, dtype=torch.float32, device=pred.device)
+        dpred = torch.empty_like(pred)
+        lib.call('rscotr_qfl_sum', pred.data_ptr(), target.data_ptr(), _ptr(weight), box_pred.data_ptr(), box_target.data_ptr(),
+                 sums.data_ptr(), dpred.data_ptr(), S, N, C, float(beta), _stream())
+        ctx.save_for_backward(dpred)
+        return sums
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        return dpred * g.view(-1, 1, 1), None, None, None, None, None
+
+
+def quality_focal_loss_sum(pred, target, box_pred, box_target, beta=2.0, weight=None):
+    """mmdet QualityFocalLoss (as the DETR / DINO heads of mmdet 3.x use it) summed per set, one kernel that also leaves the
+    gradient (rscotr_qfl_sum): pred (S,N,C) logits, target (S,N) int64 in [0,C] with C = background, box_pred / box_target
+    (S,N,4) cxcywh normalised, optional per-sample weight (S,N) -> (S,).  The quality score of a foreground row is the IoU of
+    its two boxes, a constant: box_pred gets no gradient."""
+    if not float(beta) >= 0:
+        raise ValueError(f'quality_focal_loss_sum: beta must be >= 0, got {beta}')
+    return _QFLSum.apply(pred, target, box_pred, box_target, beta, weight)
 
 
 def _upsample_args(logit, label, class_weight=None):
