@@ -35,7 +35,8 @@ extern "C" {
  * the det input chain rscotr_img_aug_chain_u8 likewise, and the Dice, Tversky, focal and Lovasz seg losses
  * rscotr_upsample_dice_* / rscotr_upsample_tversky_* / rscotr_upsample_focal_* / rscotr_upsample_lovasz_*, and the rotation input entries
  * rscotr_img_aug_rot_u8 / rscotr_seg_label_rot_u8, and the det loss entries rscotr_match_cost_kind / rscotr_box_loss_kind /
- * rscotr_qfl_sum).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
+ * rscotr_qfl_sum, and the SGD step rscotr_sgd_clip_step_r: it reads column 5 of the optimizer's per-segment table, which the AdamW
+ * entries never look at).  rscotr_version() returns the revision the shared object was BUILT with; a binding compares the two before
  * its first call (rscotr_amd/_lib.py does) — a stale .so would take a stream handle for a pointer. */
 #define RSCOTR_ABI_VERSION 11
 int rscotr_version(void);
@@ -816,6 +817,18 @@ int rscotr_adamw_clip_step_r(float* param, const float* grad, float* exp_avg, fl
 int rscotr_param_amax(const float* param, const int32_t* chunk_seg, const int64_t* chunk_off,
                       const int32_t* chunk_len, int nchunks, uint32_t* seg_amax, int nseg, uint32_t* chunk_amax,
                       void* stream);
+/* torch.optim.SGD behind the same clip, over the same arenas and tables (no second-moment arena; momentum_buf may be NULL
+ * when momentum == 0: it is then neither read nor written).  Per element of a live segment:
+ *   d = g * coef + weight_decay * p;  buf = first ? d : momentum * buf + (1 - dampening) * d;
+ *   d = nesterov ? d + momentum * buf : buf;  p -= lr * d
+ * seg_dyn rows are {lr, weight_decay, -, -, live(0/1), first(0/1), 0, 0}: `first` marks the segment's first step (a table
+ * entry, not an argument: segments go live at different iterations, and a captured step replays with a fresh table).
+ * nesterov with momentum <= 0 or dampening != 0 is refused, as torch refuses it.  sumsq is rscotr_grad_sumsq's result;
+ * seg_amax / nseg / chunk_amax as in rscotr_adamw_clip_step_r.  12 B read + 8 B written per stepped element. */
+int rscotr_sgd_clip_step_r(float* param, const float* grad, float* momentum_buf, const int32_t* chunk_seg,
+                           const int64_t* chunk_off, const int32_t* chunk_len, const float* seg_dyn, int nchunks,
+                           const float* sumsq, float max_norm, float momentum, float dampening, int nesterov,
+                           uint32_t* seg_amax, int nseg, uint32_t* chunk_amax, void* stream);
 
 /* ---- gradient exchange on RCCL, called directly ------------------------------------------------------------------------
  * Replaces the bucket all-reduces of torch DDP / c10d ProcessGroupNCCL behind the reference's MMDistributedDataParallel

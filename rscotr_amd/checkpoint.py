@@ -11,7 +11,8 @@ downsample layer are permuted.  `load_pretrained_backbone` applies it and loads 
 `save_checkpoint` / `load_checkpoint` / `resume` write and read the mmcv 1.x checkpoint layout the reference's runner
 produces (`dict(meta=..., state_dict=..., optimizer=...)`, mmcv `CheckpointHook`, cfg ...potsdam.py:218;
 `mtl/apis/train.py:109-118` resume): parameter names are the reference's, the optimizer entry is
-torch.optim.AdamW's state layout, so a reference `.pth` loads here and a checkpoint written here loads there.
+torch.optim.AdamW's state layout (torch.optim.SGD's for `FlatSGD`, whose per-tensor step counts — that layout has no slot for
+them — ride in `meta['optimizer_steps']`), so a reference `.pth` loads here and a checkpoint written here loads there.
 """
 from collections import OrderedDict
 
@@ -98,6 +99,8 @@ def save_checkpoint(path, model, optimizer=None, meta=None):
                 if torch.is_tensor(v):
                     st[k] = v.detach().cpu()
         ckpt['optimizer'] = osd
+        if hasattr(optimizer, 'step_counts'):  # (torch.optim.SGD's state layout has no step count: it rides in the meta)
+            ckpt['meta']['optimizer_steps'] = optimizer.step_counts()
     torch.save(ckpt, path)
     return ckpt
 
@@ -122,5 +125,7 @@ def resume(runner, path, map_location='cpu'):
     ckpt, report = load_checkpoint(runner.model, path, strict=True, map_location=map_location)
     if 'optimizer' in ckpt:
         runner.optimizer.load_state_dict(ckpt['optimizer'])
+        if 'optimizer_steps' in ckpt.get('meta', {}) and hasattr(runner.optimizer, 'load_step_counts'):
+            runner.optimizer.load_step_counts(ckpt['meta']['optimizer_steps'])
     runner.iter = int(ckpt.get('meta', {}).get('iter', 0))
     return ckpt

@@ -170,6 +170,62 @@ __global__ __launch_bounds__(256) void adamw_clip_kernel(
   if (chunk_amax) chunk_amax_store(chunk_amax, c, amx);
 }
 
+// torch.optim.SGD behind the same clip, over the same tables: d = g * coef + wd * p; buf = first ? d : momentum * buf + (1 - dampening) * d;
+// d = nesterov ? d + momentum * buf : buf; p -= lr * d.  `first` (column 5 of the segment's row) is "this segment's first step":
+// segments go live at different iterations and a captured step replays with a fresh table, so it cannot be a launch argument
+// (with dampening != 0 a zeroed buffer does not give torch's first step).  MOM = false (momentum == 0): there is no buffer, it is
+// neither read nor written.  12 B read + 8 B written per element (8 + 4 without momentum).
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_clip_kernel(
+    float* __restrict__ param, const float* __restrict__ grad, float* __restrict__ mom_buf,
+    const int32_t* __restrict__ chunk_seg, const int64_t* __restrict__ chunk_off, const int32_t* __restrict__ chunk_len,
+    const float* __restrict__ seg_dyn, const float* __restrict__ sumsq, float max_norm, float momentum, float omd,
+    int nesterov, unsigned* __restrict__ chunk_amax) {
+  const int c = blockIdx.x;
+  const float* d = seg_dyn + chunk_seg[c] * SEG_STRIDE;
+  if (d[4] == 0.f) return;
+  const float lr = d[0], wd = d[1];
+  const bool first = d[5] != 0.f;
+  float coef = 1.f;
+  if (max_norm > 0.f) coef = fminf(max_norm / (sqrtf(*sumsq) + 1e-6f), 1.f);  // (clip_grad_norm_, as in adamw_clip_kernel)
+  const int64_t off = chunk_off[c];
+  float4* p4 = reinterpret_cast<float4*>(param + off);
+  const float4* g4 = reinterpret_cast<const float4*>(grad + off);
+  float4* m4 = MOM ? reinterpret_cast<float4*>(mom_buf + off) : nullptr;
+  const int n4 = chunk_len[c] >> 2;
+  float amx = 0.f;
+  // (`first` and `nesterov` are workgroup-uniform: selects, no divergence)
+#define RSCOTR_SGD_1(X)                                      \
+  {                                                          \
+    float dd = g.X * coef + wd * p.X;                        \
+    if (MOM) {                                               \
+      m.X = first ? dd : momentum * m.X + omd * dd;          \
+      dd = nesterov ? dd + momentum * m.X : m.X;             \
+    }                                                        \
+    p.X -= lr * dd;                                          \
+  }
+  auto step4 = [&](int i, float4 p, const float4& g, float4 m) {
+    RSCOTR_SGD_1(x) RSCOTR_SGD_1(y) RSCOTR_SGD_1(z) RSCOTR_SGD_1(w)
+    p4[i] = p;
+    if (MOM) m4[i] = m;
+    amx = fmaxf(fmaxf(amx, fmaxf(fabsf(p.x), fabsf(p.y))), fmaxf(fabsf(p.z), fabsf(p.w)));
+  };
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  // two elements of the thread's stride requested before either is stepped (the loop shape of adamw_clip_kernel)
+  int i = threadIdx.x;
+  for (; i + 256 < n4; i += 512) {
+    const int j = i + 256;
+    const float4 p0 = p4[i], g0 = g4[i], m0 = MOM ? m4[i] : zero;
+    const float4 p1 = p4[j], g1 = g4[j], m1 = MOM ? m4[j] : zero;
+    asm volatile("" ::: "memory");  // (all requests before the first store)
+    step4(i, p0, g0, m0);
+    step4(j, p1, g1, m1);
+  }
+  if (i < n4) step4(i, p4[i], g4[i], MOM ? m4[i] : zero);
+#undef RSCOTR_SGD_1
+  if (chunk_amax) chunk_amax_store(chunk_amax, c, amx);
+}
+
 }  // namespace rscotr
 
 using namespace rscotr;
@@ -239,4 +295,38 @@ extern "C" int rscotr_adamw_clip_step_r(float* param, const float* grad, float* 
   if (ranges)
     seg_amax_reduce_kernel<<<dim3((nseg + 3) / 4), dim3(256), 0, (hipStream_t)stream>>>(chunk_seg, chunk_amax, seg_dyn, seg_amax, nseg, nchunks);
   return check_launch("rscotr_adamw_clip_step");
+}
+
+extern "C" int rscotr_sgd_clip_step_r(float* param, const float* grad, float* momentum_buf, const int32_t* chunk_seg,
+                                      const int64_t* chunk_off, const int32_t* chunk_len, const float* seg_dyn, int nchunks,
+                                      const float* sumsq, float max_norm, float momentum, float dampening, int nesterov,
+                                      uint32_t* seg_amax, int nseg, uint32_t* chunk_amax, void* stream) {
+  if (nchunks < 0 || nseg < 0) return fail(RSCOTR_E_SHAPE, "rscotr_sgd_clip_step_r: negative count");
+  // (torch.optim.SGD's own refusals)
+  if (!(momentum >= 0.f)) return fail(RSCOTR_E_ARG, "rscotr_sgd_clip_step_r: momentum must be >= 0");
+  if (nesterov && (momentum <= 0.f || dampening != 0.f))
+    return fail(RSCOTR_E_ARG, "rscotr_sgd_clip_step_r: Nesterov momentum requires a momentum and zero dampening");
+  if (nchunks == 0) return RSCOTR_OK;
+  const bool mom = momentum != 0.f;
+  if (!param || !grad || (mom && !momentum_buf) || !chunk_seg || !chunk_off || !chunk_len || !seg_dyn)
+    return fail(RSCOTR_E_ARG, "rscotr_sgd_clip_step_r: null pointer");
+  if (max_norm > 0.f && !sumsq) return fail(RSCOTR_E_ARG, "rscotr_sgd_clip_step_r: sumsq required when clipping");
+  if (!aligned16(param) || !aligned16(grad) || (mom && !aligned16(momentum_buf)))
+    return fail(RSCOTR_E_ALIGN, "rscotr_sgd_clip_step_r: arenas must be 16-byte aligned");
+  const bool ranges = seg_amax && nseg > 0;
+  if (ranges && !chunk_amax) return fail(RSCOTR_E_ARG, "rscotr_sgd_clip_step_r: chunk_amax (4 * nchunks words) required with seg_amax");
+  if (ranges && !aligned16(chunk_amax)) return fail(RSCOTR_E_ALIGN, "rscotr_sgd_clip_step_r: chunk_amax must be 16-byte aligned");
+  // (work 0, as for the AdamW step: 20 bytes per stepped element, 12 without momentum)
+  ProfScope prof(PROF_HBM, 0.0, (hipStream_t)stream, "rscotr::sgd_clip_kernel");
+  const float omd = (float)(1.0 - (double)dampening);
+  unsigned* ca = ranges ? chunk_amax : nullptr;
+  if (mom)
+    sgd_clip_kernel<true><<<dim3(nchunks), dim3(256), 0, (hipStream_t)stream>>>(
+        param, grad, momentum_buf, chunk_seg, chunk_off, chunk_len, seg_dyn, sumsq, max_norm, momentum, omd, nesterov, ca);
+  else
+    sgd_clip_kernel<false><<<dim3(nchunks), dim3(256), 0, (hipStream_t)stream>>>(
+        param, grad, nullptr, chunk_seg, chunk_off, chunk_len, seg_dyn, sumsq, max_norm, 0.f, omd, 0, ca);
+  if (ranges)
+    seg_amax_reduce_kernel<<<dim3((nseg + 3) / 4), dim3(256), 0, (hipStream_t)stream>>>(chunk_seg, chunk_amax, seg_dyn, seg_amax, nseg, nchunks);
+  return check_launch("rscotr_sgd_clip_step_r");
 }

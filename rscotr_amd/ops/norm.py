@@ -129,6 +129,8 @@ class _LayerNormFork(Function):
     @staticmethod
     def backward(ctx, dy, dres):
         if dy is None:  # norm output unused: only the residual gradient flows
+            if STATE.grad_sink is not None:  # (... and the norm's parameters have NOT received a gradient, whatever their hooks see)
+                STATE.grad_sink.no_gradient(ctx.saved_tensors[1], ctx.bias)
             return dres, None, None, None, None
         return _LayerNorm._backward(ctx, dy, dres) + (None,)
 

@@ -16,7 +16,7 @@ import torch
 from .dist import GradSync, is_dist
 from .mtl import LazyLogVars
 from . import ops
-from .optim import StepLrUpdater, build_optimizer
+from .optim import LrUpdater, build_optimizer
 
 
 _HOST_TIMES = os.environ.get('RSCOTR_HOST_TIMES') == '1'
@@ -393,8 +393,8 @@ class IterBasedRunner:
         self.model, self.optimizer, self.data_loader = model, optimizer, data_loader
         self.iter = 0
         self.lr_updater = None
-        if lr_config and lr_config.get('policy') == 'step':
-            self.lr_updater = StepLrUpdater(**{k: v for k, v in lr_config.items() if k != 'policy'})
+        if lr_config:  # (every key of it is honoured or refused by name: rscotr_amd.optim.LrUpdater)
+            self.lr_updater = LrUpdater(**dict(lr_config))
         self.log_interval, self.logger = log_interval, logger
         if bucket_mb is None:  # gradient exchange granularity (MB of fp32 gradients per all-reduce)
             from .dist import INLINE
@@ -462,7 +462,10 @@ class IterBasedRunner:
         if self.rnd_fn is not None:
             batch = dict(batch, rnd=self.rnd_fn(batch))
         if self.lr_updater is not None:
-            self.optimizer.set_lr_factor(self.lr_updater.factor(self.iter))
+            # the rates of this iteration, one per parameter group: a function of `iter` alone (a resumed run needs nothing
+            # more), written into the step's host table by prepare_step — no device work, and a replayed graph reads them
+            # from its own table
+            self.optimizer.set_lrs(self.lr_updater.rates(self.optimizer.base_lr, self.iter, self.max_iters))
         task = self.last_task = batch['task']
         if task in self.graph_tasks and batch['img'].is_cuda and not self.force_eager:
             # first iteration of a task runs eagerly (parameter liveness, workspaces); the second
